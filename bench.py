@@ -12,7 +12,14 @@ exchange step).  Shards are independent per rank (weak scaling:
 every rank verifies its own 1,048,576 signatures, index shard
 stl_shard_range(N*n, rank, N)).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--per-gpu N_SIGS]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--per-gpu N_SIGS] [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed
+steps, the line.  --dump-outputs DIR also writes the last timed step's accept
+bitmap as DIR/accepted.npy (float32, one 0/1 value per signature; the inputs
+are seeded, so two builds can be compared output for output).  --full adds,
+after the timed steps, everything else described below: the per-kernel pass
+and its roofline, extra_configs, end_to_end, cpu_baseline.
 
 With N > 1 and no WORLD_SIZE in the environment this process is only a
 launcher: it starts `python -m torch.distributed.run --nproc-per-node N ...
@@ -23,10 +30,11 @@ plane is libstl (verify kernels + RCCL gather).  --dry-run rehearses the
 launcher, sharding, control plane and JSON line on CPUs only (no GPU, no
 verification; the line says so).
 
-Prints ONE JSON line on rank 0.  roofline: integer-VALU bound; achieved =
-W_VERIFY int ops per verify (frozen) x verifies per launch /
-average launch time measured with HIP events on the launch stream.
-cpu_baseline: the reference's verify call path (libsodium 1.0.18
+Prints ONE JSON line on rank 0.  roofline: integer-VALU bound; achieved_launch
+= W_VERIFY int ops per verify (frozen) x verifies per launch /
+average launch time measured with HIP events on the launch stream; with --full
+also the main kernel's own figures from libstl's phase clock.
+cpu_baseline (--full): the reference's verify call path (libsodium 1.0.18
 crypto_sign_verify_detached + stellard S<L, oracle/_ref/libsodium_ref.so) --
 or the oracle port when libsodium is absent -- on bounded samples at T = all
 affinity CPUs, 16 (the GPU box's CPU share), the cgroup quota, 6 (stellard's
@@ -91,7 +99,31 @@ def parse():
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the configs[2] / configs[4] / config-1 legs and the end_to_end leg (profiling runs: "
                          "only the bench batch's own launches are traced)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the per-kernel "
+                         "phase-clock pass and the roofline built on it, the extra_configs legs, end_to_end and "
+                         "cpu_baseline (--no-extra / --no-cpu-baseline / --cpu-* narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32): accepted = rank 0's "
+                         "accept bitmap, one 0/1 value per signature (the gathered bitmap at N > 1)")
     return ap.parse_args()
+
+
+# --dump-outputs writes at most this many bytes in all
+DUMP_CAP_BYTES = 60_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """Each array as DIR/<name>.npy in float32.  An array over its share of
+    DUMP_CAP_BYTES is cut to a fixed, seeded sample of its elements (sorted
+    indices: the same ones in every run of the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = (DUMP_CAP_BYTES // len(arrays) - 1024) // 4
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0x5EEDD0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
 
 
 # ------------------------------------------------------------------ launcher
@@ -432,6 +464,8 @@ def dry_run(args, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t[0])
     ok = bool(shard.words_to_bool(full, n * world).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accepted": shard.words_to_bool(full, n * world)})
     from tools import bench_legs as BL
     ctx = {"world": world, "rank": rank, "dist": dist, "sync": lambda: None,
            "gather": BL.Gather(world, rank, dist, "gloo")}
@@ -625,10 +659,93 @@ def gpu_run(args, world, rank, local):
             assert gathered_check["all_accepted"], "gathered bitmap has rejects"
 
     st = V.get_stats()  # device counters over the K timed launches (after the sync above)
-    # ---- per-kernel timing pass (after the timed region): K more launches with
-    # libstl's phase clock -- HIP events recorded on the launch stream between
-    # the kernels of each launch, which runs its kernels one after another (no
-    # concurrent chunks), so each duration is that kernel's alone ----
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last timed step holds: the accept bitmap
+        # (gathered from every rank at N > 1), before any later leg reuses the buffers
+        dump_outputs(args.dump_outputs, {"accepted": V.words_to_bool(full_words if world > 1 else words, n * world)})
+    if rank == 0:
+        line = headline(args, world, n, dt, kern_ms, (clock_ghz, clock_xcc, clock_cus), V.execution_settings(),
+                        {"gather": gather_via, "rccl_nranks": rccl_nranks, "gather_check": gathered_check}, st)
+    if args.full:
+        full_report(args, world, rank, line if rank == 0 else None, kern_ms,
+                    {"dist": dist, "V": V, "torch": torch, "dev": dev, "stream": stream, "gather": gather_into},
+                    (sig, msgs, pk, words))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        if gather_into.mode == "rccl":
+            V.comm_destroy()
+        dist.destroy_process_group()
+
+
+def headline(args, world, n, dt, kern_ms, clock, execution, gather, st):
+    """Rank 0's result line of a plain run: the timed steps' figures only.
+    roofline holds what the timed launches' own HIP events give; the
+    per-kernel figures take launches of their own (--full, full_report)."""
+    clock_ghz, clock_xcc, clock_cus = clock
+    per_launch = n / (kern_ms * 1e-3)
+    achieved_launch = W_VERIFY * per_launch / 1e12
+    return {
+        "metric": "Ed25519 tx verifies/sec",
+        "value": n * world * args.steps / dt,
+        "unit": "verifies/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt * 1e3 / args.steps,
+        "clock_ghz": clock_ghz,
+        "cycles_per_verify": (dt / args.steps) * clock_ghz * 1e9 / n if clock_ghz else None,
+        "clock": {"per_xcc_ghz": clock_xcc, "cus_matched": clock_cus,
+                  "how": "stl_debug_clock_stamp (one wave per workgroup, 256 workgroups) right before and "
+                         "right after the timed region: per CU, d(s_memtime) / d(s_memrealtime) x 100 MHz, "
+                         "median over the CUs stamped both times (rank 0's GPU); cycles_per_verify = "
+                         "ms_per_step x clock_ghz / signatures per GPU"},
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic: GPU-signed RFC 8032 signatures over seeded random keys and 32-byte signing hashes",
+        "full": bool(args.full),
+        "config": {"workload": "configs[1]: 1,048,576 fixed-size Payment-tx signatures per GPU "
+                               "(stl_ed25519_verify_batch_device, policy libsodium-1.0.18 + S<L)",
+                   "signatures_per_gpu": n,
+                   "parallelism": f"dp{world} (index shards, RCCL bitmap gather to rank 0)"
+                                  if world > 1 else "dp1",
+                   "gather": gather["gather"], "rccl_nranks": gather["rccl_nranks"],
+                   "gather_check": gather["gather_check"],
+                   "execution": dict(execution,
+                                     stream_pool="libstl: 2 kernel + 1 copy streams per device, made in "
+                                                 "stl_init before any caller stream (DESIGN.md section 8); "
+                                                 "chunk_log2 0 = round(n / 2^18) equal chunks")},
+        "roofline": {"bound": "valu", "peak": PEAK_INT_OPS / 1e12, "unit": "Tops/s",
+                     "algorithmic_bytes": BYTES_PER_VERIFY * n,
+                     "work_model": "W_VERIFY = 64*1520 M + 36*1525 S + 5520 (ref10 verify) = %d ops; main "
+                                   "kernel W_MAIN = W_VERIFY - W_PREP = %d, prep W_PREP = SHA-512 block + two "
+                                   "decompressions = %d" % (W_VERIFY, W_MAIN, W_PREP),
+                     "launch_ms": kern_ms, "achieved_launch": achieved_launch,
+                     "frac_launch": achieved_launch * 1e12 / PEAK_INT_OPS,
+                     "launch": "every kernel of one stl_ed25519_verify_batch_device call (phase 1, main, "
+                               "fallback), HIP events around each call of the timed region",
+                     "hbm_frac": BYTES_PER_VERIFY * per_launch / (HBM_PEAK_GBS * 1e9)},
+        "cpu_baseline": None,
+        "stats": {"source": "stl_get_stats over the timed launches (rank 0)",
+                  "accepted": st["accepted"], "full_length_lanes": st["full_length_lanes"],
+                  "verifies": n * args.steps},
+        "extra_configs": None,
+    }
+
+
+def full_report(args, world, rank, line, kern_ms, ctx, batch):
+    """--full: everything past the headline figure, run after the timed
+    region on every rank (the legs gather); rank 0 adds the results to
+    ``line`` (None on the other ranks)."""
+    V, torch, stream = ctx["V"], ctx["torch"], ctx["stream"]
+    sig, msgs, pk, words = batch
+    n = args.n
+    # ---- per-kernel timing pass: K more launches with libstl's phase clock --
+    # HIP events recorded on the launch stream between the kernels of each
+    # launch, which runs its kernels one after another (no concurrent chunks),
+    # so each duration is that kernel's alone ----
     V.set_phase_timing(True)
     V.reset_stats()
     for _ in range(args.steps):
@@ -638,21 +755,15 @@ def gpu_run(args, world, rank, local):
     V.set_phase_timing(False)
     extra = None
     if not args.no_extra:
-        ctx = {"world": world, "rank": rank, "dist": dist, "V": V, "torch": torch, "dev": dev, "stream": stream,
-               "sync": torch.cuda.synchronize, "gather": gather_into}
-        extra = extra_configs(ctx)
+        extra = extra_configs(dict(ctx, world=world, rank=rank, sync=torch.cuda.synchronize))
     chunks = max(1, pst["phase_chunks"])
     phase_ms = {k: v / chunks / 1e6 for k, v in pst["phase_ns"].items()}  # average per launch (one chunk each)
     if rank == 0:
-        total = n * world * args.steps
-        value = total / dt
-        per_launch = n / (kern_ms * 1e-3)
         # the dominant kernel (verify_main_kernel): algorithmic work of one
         # launch (W_VERIFY x n) / its average duration, live HIP events
         main_ms = phase_ms["main"]
         prep_ms = phase_ms["phase1"]
         achieved = W_MAIN * n / (main_ms * 1e-3) / 1e12
-        achieved_launch = W_VERIFY * per_launch / 1e12
         traffic, traffic_build = None, None
         from stellard_amd.build import source_digest
         digest = source_digest()
@@ -683,73 +794,28 @@ def gpu_run(args, world, rank, local):
                          "per_kernel_pct": {k: v.get("VALUBusy") for k, v in vd.get("kernels", {}).items()},
                          "source": vd.get("source", "rocprofv3 --pmc VALUBusy, profiles/valu_latest.json"),
                          "build": provenance(vd, vp)}
-        line = {
-            "metric": "Ed25519 tx verifies/sec",
-            "value": value,
-            "unit": "verifies/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt * 1e3 / args.steps,
-            "clock_ghz": clock_ghz,
-            "cycles_per_verify": (dt / args.steps) * clock_ghz * 1e9 / n if clock_ghz else None,
-            "clock": {"per_xcc_ghz": clock_xcc, "cus_matched": clock_cus,
-                      "how": "stl_debug_clock_stamp (one wave per workgroup, 256 workgroups) right before and "
-                             "right after the timed region: per CU, d(s_memtime) / d(s_memrealtime) x 100 MHz, "
-                             "median over the CUs stamped both times (rank 0's GPU); cycles_per_verify = "
-                             "ms_per_step x clock_ghz / signatures per GPU"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic: GPU-signed RFC 8032 signatures over seeded random keys and 32-byte signing hashes",
-            "config": {"workload": "configs[1]: 1,048,576 fixed-size Payment-tx signatures per GPU "
-                                   "(stl_ed25519_verify_batch_device, policy libsodium-1.0.18 + S<L)",
-                       "signatures_per_gpu": n,
-                       "parallelism": f"dp{world} (index shards, RCCL bitmap gather to rank 0)"
-                                      if world > 1 else "dp1",
-                       "gather": gather_via, "rccl_nranks": rccl_nranks, "gather_check": gathered_check,
-                       "execution": dict(V.execution_settings(),
-                                         stream_pool="libstl: 2 kernel + 1 copy streams per device, made in "
-                                                     "stl_init before any caller stream (DESIGN.md section 8); "
-                                                     "chunk_log2 0 = round(n / 2^18) equal chunks",
-                                         overlap={"serial_kernel_sum_ms": sum(phase_ms.values()),
-                                                  "launch_ms": kern_ms,
-                                                  "ratio": kern_ms / max(1e-9, sum(phase_ms.values())),
-                                                  "reading": "ratio < 1: the chunks on the pool's two kernel "
-                                                             "streams overlapped; >= 1: they ran one after "
-                                                             "another (e.g. streams sharing a hardware queue)"})},
-            "roofline": {"bound": "valu", "achieved": achieved, "peak": PEAK_INT_OPS / 1e12, "unit": "Tops/s",
-                         "frac": achieved * 1e12 / PEAK_INT_OPS, "traffic": traffic,
-                         "per_kernel": per_kernel(vd, n, {"verify_prep_kernel": (W_PREP, prep_ms),
-                                                          "verify_main_kernel": (W_MAIN, main_ms)}),
-                         "algorithmic_bytes": BYTES_PER_VERIFY * n,
-                         "traffic_over_algorithmic": traffic / (BYTES_PER_VERIFY * n) if traffic else None,
-                         "traffic_build": traffic_build, "sources_sha256": digest,
-                         "kernel": "verify_main_kernel (dominant: %.0f %% of the launch)"
-                                   % (100.0 * main_ms / max(1e-9, sum(phase_ms.values()))),
-                         "kernel_ms": main_ms, "work_per_verify": W_MAIN, "units_per_launch": n,
-                         "work_model": "W_VERIFY = 64*1520 M + 36*1525 S + 5520 (ref10 verify) = %d ops; main "
-                                       "kernel W_MAIN = W_VERIFY - W_PREP = %d, prep W_PREP = SHA-512 block + two "
-                                       "decompressions = %d" % (W_VERIFY, W_MAIN, W_PREP),
-                         "timing": "libstl phase events (stl_set_phase_timing) on the launch stream over K "
-                                   "launches right after the timed region (kernels one after another); work = "
-                                   "W_MAIN x n per launch, the part of W_VERIFY the main kernel does",
-                         "frac_all_work_on_main": W_VERIFY * n / (main_ms * 1e-3) / PEAK_INT_OPS,
-                         "phase_ms": phase_ms,
-                         "launch_ms": kern_ms, "achieved_launch": achieved_launch,
-                         "frac_launch": achieved_launch * 1e12 / PEAK_INT_OPS,
-                         "launch": "every kernel of one stl_ed25519_verify_batch_device call (phase 1, main, "
-                                   "fallback), HIP events around each call of the timed region",
-                         "hbm_frac": BYTES_PER_VERIFY * per_launch / (HBM_PEAK_GBS * 1e9),
-                         "valu_busy_pmc": valu_busy,
-                         "issue_bound": issue},
-            "cpu_baseline": None,
-            "stats": {"source": "stl_get_stats over the timed launches (rank 0)",
-                      "accepted": st["accepted"], "full_length_lanes": st["full_length_lanes"],
-                      "verifies": n * args.steps},
-            "extra_configs": extra,
-        }
+        line["config"]["execution"]["overlap"] = {
+            "serial_kernel_sum_ms": sum(phase_ms.values()), "launch_ms": kern_ms,
+            "ratio": kern_ms / max(1e-9, sum(phase_ms.values())),
+            "reading": "ratio < 1: the chunks on the pool's two kernel streams overlapped; >= 1: they ran one "
+                       "after another (e.g. streams sharing a hardware queue)"}
+        line["roofline"].update({
+            "achieved": achieved, "frac": achieved * 1e12 / PEAK_INT_OPS, "traffic": traffic,
+            "per_kernel": per_kernel(vd, n, {"verify_prep_kernel": (W_PREP, prep_ms),
+                                             "verify_main_kernel": (W_MAIN, main_ms)}),
+            "traffic_over_algorithmic": traffic / (BYTES_PER_VERIFY * n) if traffic else None,
+            "traffic_build": traffic_build, "sources_sha256": digest,
+            "kernel": "verify_main_kernel (dominant: %.0f %% of the launch)"
+                      % (100.0 * main_ms / max(1e-9, sum(phase_ms.values()))),
+            "kernel_ms": main_ms, "work_per_verify": W_MAIN, "units_per_launch": n,
+            "timing": "libstl phase events (stl_set_phase_timing) on the launch stream over K "
+                      "launches right after the timed region (kernels one after another); work = "
+                      "W_MAIN x n per launch, the part of W_VERIFY the main kernel does",
+            "frac_all_work_on_main": W_VERIFY * n / (main_ms * 1e-3) / PEAK_INT_OPS,
+            "phase_ms": phase_ms,
+            "valu_busy_pmc": valu_busy,
+            "issue_bound": issue})
+        line["extra_configs"] = extra
         if world == 1 and not args.no_extra:
             try:
                 line["end_to_end"] = end_to_end(V, torch, sig, msgs, pk)
@@ -757,7 +823,7 @@ def gpu_run(args, world, rank, local):
                 line["end_to_end"] = {"error": repr(e)}
         if world == 1 and not args.no_extra:
             try:
-                c1 = config1_leg(V, torch, dev, stream, args.cpu_threads)
+                c1 = config1_leg(V, torch, ctx["dev"], stream, args.cpu_threads)
             except Exception as e:  # noqa: BLE001
                 c1 = {"error": repr(e)}
             line["extra_configs"] = dict(line["extra_configs"] or {}, config1_payment_checksign_100k=c1)
@@ -767,11 +833,6 @@ def gpu_run(args, world, rank, local):
                                                     args.cpu_threads, args.cpu_reps)
             except Exception as e:  # noqa: BLE001 - the baseline must not kill the GPU number
                 line["cpu_baseline"] = {"error": repr(e)}
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        if gather_into.mode == "rccl":
-            V.comm_destroy()
-        dist.destroy_process_group()
 
 
 def main():

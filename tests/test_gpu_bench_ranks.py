@@ -1,5 +1,5 @@
 """The multi-rank bench flow on the GPU box (-m gpu): `bench.py --gpus 2
---gather gloo` starts two ranks (torch.distributed.run) that both use the one
+--gather gloo --full` starts two ranks (torch.distributed.run) that both use the one
 visible MI355X -- RCCL refuses two ranks on one device, so the bitmap words are
 gathered through host memory with gloo -- and runs everything else of the
 driver's SCALE path: per-rank shards, barriers, max-over-ranks timing, the
@@ -22,12 +22,41 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times its steps and prints the line -- no per-kernel pass,
+    no extra legs, no CPU baseline (those are --full) -- and --dump-outputs
+    writes the last timed step's accept bitmap as float32, one value per
+    signature (4,160: 65 ballot words, the last wave partly filled)."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    n = 4160
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--per-gpu", str(n), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    lines = [s for s in r.stdout.strip().splitlines() if s.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "Ed25519 tx verifies/sec" and line["unit"] == "verifies/s" and line["dtype"] == "u32"
+    assert line["higher_is_better"] is True and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["stats"]["accepted"] == line["stats"]["verifies"] == n * 3  # exactly the timed steps ran
+    assert line["full"] is False and line["extra_configs"] is None and line["cpu_baseline"] is None
+    assert "end_to_end" not in line and "phase_ms" not in line["roofline"]
+    assert os.listdir(tmp_path / "out") == ["accepted.npy"]
+    acc = np.load(tmp_path / "out" / "accepted.npy", allow_pickle=False)
+    assert acc.dtype == np.float32 and acc.shape == (n,) and (acc == 1.0).all()
+
+
 @pytest.mark.timeout(600)
 def test_bench_two_ranks_gloo_rehearsal():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "gloo", "--full",
                         "--steps", "2", "--warmup", "1", "--per-gpu", "65536", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])

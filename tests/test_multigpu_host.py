@@ -53,6 +53,35 @@ def test_bench_launcher_dry_run(gpus):
     assert line["metric"].startswith("DRY RUN")
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the gathered accept bitmap of the last
+    step as DIR/accepted.npy, float32, one value per signature of every rank
+    (the dry run's words are all ones)."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1",
+                        "--warmup", "0", "--per-gpu", "4160", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert _last_json(r.stdout)["steps"] == 1
+    assert os.listdir(tmp_path / "out") == ["accepted.npy"]
+    acc = np.load(tmp_path / "out" / "accepted.npy", allow_pickle=False)
+    assert acc.dtype == np.float32 and acc.shape == (2 * 4160,) and (acc == 1.0).all()
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """An output over the byte cap is cut to a seeded sample: the same
+    elements in every call, in order, within the cap."""
+    import bench
+    big = np.arange(bench.DUMP_CAP_BYTES // 4 + 1000, dtype=np.float64) % 1021
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": big, "small": np.ones(5, bool)})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < a.size < big.size
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.ones(5, np.float32))
+
+
 @pytest.mark.parametrize("gpus,fault", [(1, None), (2, None), (4, None), (2, "shift"), (2, "dup"), (4, "zero")])
 def test_bench_digest_rehearsal_catches_bad_gather(gpus, fault):
     """the multi-rank legs must be able to FAIL.  The dry run

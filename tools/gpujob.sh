@@ -9,8 +9,8 @@
 #   suite              pytest -m gpu (the round-end suite)
 #   tests:F1,F2        pytest -m gpu on the named test files / node ids only
 #   smoke              __graft_entry__.smoke()
-#   bench              python bench.py (defaults: the driver's N = 1 line)
-#   bench2             bench.py --gpus 2 --gather gloo (multi-rank rehearsal on one GPU)
+#   bench              python bench.py --full (defaults: the N = 1 line with every leg)
+#   bench2             bench.py --gpus 2 --gather gloo --full (multi-rank rehearsal on one GPU)
 #   profile            tools/profile.sh: kernel trace + FETCH/WRITE/SQ PMC passes
 #   valu               tools/valu_pmc.sh: VALUBusy / INT64 / occupancy PMC passes
 #   ab:K:R:V1,V2       ABBA of libstl builds build/ab/V.so ("base" = stellard_amd/libstl.so),
@@ -50,8 +50,8 @@ for step in "$@"; do
       T=${step#tests:}
       run pytest_gpu_part 900 python -u -m pytest ${T//,/ } -m gpu -x -v --timeout 300 --timeout-method thread || exit $? ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 600 python -u bench.py || exit $? ;;
-    bench2) run bench_n2_rehearsal 600 python -u bench.py --gpus 2 --gather gloo --no-cpu-baseline || exit $? ;;
+    bench) run bench 600 python -u bench.py --full || exit $? ;;
+    bench2) run bench_n2_rehearsal 600 python -u bench.py --gpus 2 --gather gloo --full --no-cpu-baseline || exit $? ;;
     profile) run profile 900 bash tools/profile.sh $OUT/prof || exit $? ;;
     valu) run valu 900 bash tools/valu_pmc.sh $OUT/valu || exit $? ;;
     ab:*)
