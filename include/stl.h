@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define STL_ABI_VERSION 3
+#define STL_ABI_VERSION 4
 
 /* ---- return codes ---- */
 #define STL_OK 0
@@ -507,6 +507,63 @@ int stl_ed25519_sign_batch_device(const uint8_t *d_seed, const uint8_t *d_msg, s
 int stl_debug_sign_adversarial_device(const uint8_t *d_seed, const uint8_t *d_msg, const uint8_t *d_cls,
                                       const uint32_t *d_param, size_t n, uint8_t *d_pk, uint8_t *d_sig,
                                       uint8_t *d_msg_out, void *stream);
+
+/* ---- registered signer sets (keysets) ----
+ * For signers known in advance -- stellard's UNL validators (validations and
+ * proposals), a ledger's funded accounts -- libstl keeps, per key, a
+ * fixed-window table of j * 2^(8w) * (-A) on the device (and one of B), so a
+ * verification is 64 table additions and no doubling:
+ * encode([S]B + [k](-A)) == R, the predicate of the per-signature calls bit
+ * for bit (the table is built on the decoded point itself, so mixed-order,
+ * small-order, non-canonical and undecodable keys answer as they do there
+ * under the call's policy).  A row names its signer by its index in the set.
+ * A keyset lives on one device (the calling thread's current device at
+ * creation; the multi-GPU sharding of the host batch calls does not apply) and
+ * holds table_bytes of device memory: 512 KiB per key plus the base table. */
+#define STL_KEYSET_MAX_KEYS 4096u  /* 2 GiB of tables */
+#define STL_KEYSET_BASE 0xFFFFFFFFu /* stl_debug_keyset_rows: the base point's table */
+typedef struct stl_keyset stl_keyset;
+typedef struct stl_keyset_info {
+  uint32_t struct_size; /* sizeof(stl_keyset_info) */
+  uint32_t nkeys;
+  uint32_t window_bits, windows, rows_per_window, row_bytes; /* table geometry: signed digits of
+                                                                window_bits bits, rows |j| = 1..rows_per_window */
+  int32_t device;       /* HIP device ordinal */
+  uint32_t reserved;
+  uint64_t table_bytes; /* device memory of the tables, the base point's included */
+} stl_keyset_info;
+/* pk: nkeys * 32 bytes, host memory; nkeys in 1..STL_KEYSET_MAX_KEYS; duplicates allowed; flags 0.
+ * Synchronous: decodes the keys and builds the tables on the device before returning (the build's
+ * scratch is freed again).  STL_OK and *out, or a negative code and *out = NULL. */
+int stl_keyset_create(const uint8_t *pk, size_t nkeys, uint32_t flags, stl_keyset **out);
+/* Waits for the device work using the keyset, then frees it.  NULL, a destroyed handle and a
+ * handle from before stl_shutdown (which frees every keyset) are ignored. */
+void stl_keyset_destroy(stl_keyset *ks);
+int stl_keyset_get_info(const stl_keyset *ks, stl_keyset_info *out);
+/* First index of the 32-byte key in the set, or -1 (also for a handle that is not live); a host-side map. */
+long long stl_keyset_find(const stl_keyset *ks, const uint8_t pk[32]);
+/* Row i is (key_index[i], sig[64 i..], msg[32 i..]).  flags: the policy bit, STL_REQUIRE_S_LT_L,
+ * STL_DEBUG_RAW_PREDICATE; anything else is STL_EINVAL (the execution flags do not apply).  A handle
+ * that is not live, or a call on another device than the keyset's, is STL_EINVAL.
+ * Host form: host memory, synchronous; a key_index >= nkeys is STL_EINVAL (nothing is verified). */
+int stl_keyset_verify_batch(stl_keyset *ks, const uint32_t *key_index, const uint8_t *sig, const uint8_t *msg,
+                            size_t n, uint8_t *accept_bitmap, uint32_t flags);
+/* Device form: device memory, enqueued on `stream`, bitmap words as stl_ed25519_verify_batch_device
+ * writes them.  The indices are not visible to the host here: a row whose key_index >= nkeys gets
+ * accept bit 0 (and reads no table); the other rows are unaffected. */
+int stl_keyset_verify_batch_device(stl_keyset *ks, const uint32_t *d_key_index, const uint8_t *d_sig,
+                                   const uint8_t *d_msg, size_t n, uint64_t *d_bitmap_words, uint32_t flags,
+                                   void *stream);
+/* checkSign / validation form: SHA512Half of every signing preimage (the kernel of
+ * stl_tx_hash_batch_device) into the stream context's scratch, then the keyset verify: the same
+ * bits as that call followed by stl_keyset_verify_batch_device. */
+int stl_keyset_tx_verify_batch_device(stl_keyset *ks, const uint32_t *d_key_index, const uint8_t *d_preimages,
+                                      const uint64_t *d_offset, const uint32_t *d_len, const uint8_t *d_sig,
+                                      size_t n, uint64_t *d_bitmap_words, uint32_t flags, void *stream);
+/* Test hook: nrows table rows from first_row (row = w * rows_per_window + j - 1) of key `key`
+ * (STL_KEYSET_BASE: the base point's table) copied to host memory, row_bytes / 4 words each. */
+int stl_debug_keyset_rows(const stl_keyset *ks, uint32_t key, uint32_t first_row, uint32_t nrows,
+                          uint32_t *out_words);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,10 @@ STL_ONE_LANE = 0x10
 STL_NO_AUTO_DEDUP = 0x20
 STL_DEBUG_RAW_PREDICATE = 0x80000000  # test-only: no S < L (stl.h)
 
+# registered signer sets (stl_keyset_*)
+STL_KEYSET_MAX_KEYS = 4096
+STL_KEYSET_BASE = 0xFFFFFFFF
+
 # stl_debug_tuning keys
 STL_TUNE_FUSED_PREP = 0
 STL_TUNE_MAIN_QUEUE = 1
@@ -111,6 +115,16 @@ SYMBOLS = [
     ("stl_release_stream", ctypes.c_int, [_P]),
     ("stl_debug_sign_adversarial_device", ctypes.c_int,
      [_U8P, _U8P, _U8P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),
+    ("stl_keyset_create", ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.c_uint32, _P]),
+    ("stl_keyset_destroy", None, [_P]),
+    ("stl_keyset_get_info", ctypes.c_int, [_P, _P]),
+    ("stl_keyset_find", ctypes.c_longlong, [_P, _U8P]),
+    ("stl_keyset_verify_batch", ctypes.c_int, [_P, _P, _U8P, _U8P, ctypes.c_size_t, _U8P, ctypes.c_uint32]),
+    ("stl_keyset_verify_batch_device", ctypes.c_int,
+     [_P, _P, _U8P, _U8P, ctypes.c_size_t, _P, ctypes.c_uint32, _P]),
+    ("stl_keyset_tx_verify_batch_device", ctypes.c_int,
+     [_P, _P, _U8P, _P, _P, _U8P, ctypes.c_size_t, _P, ctypes.c_uint32, _P]),
+    ("stl_debug_keyset_rows", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -3,6 +3,7 @@
   stellard_amd/libstl.so         product: gfx950 kernels + C ABI (hipcc)
   tests/native/libhostemu.so     test harness: the device verify code compiled
                                  for the host (bound checks on)
+  tests/native/libhostemu_keyset.so  the same for the keyset's comb code
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -18,9 +19,10 @@ CSRC = os.path.join(ROOT, "stellard_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-PRODUCT_SRCS = ["stl_kernels.hip", "stl_api.cpp", "stl_batcher.cpp"]
+PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_api.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
+                               "stl_comb.h", "stl_keyset.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
 
@@ -51,7 +53,7 @@ def _run(cmd, cwd=ROOT):
 # per-object dependencies: the host sources see only the ABI header and the
 # launcher declarations, so a host-side change does not recompile the kernels
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
-HOST_DEPS = ["stl_kernels.h", os.path.join("..", "..", "include", "stl.h")]
+HOST_DEPS = ["stl_kernels.h", "stl_keyset.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -72,7 +74,12 @@ def build_product(force=False, extra_flags=(), variant="variant"):
     objs = []
     for src in PRODUCT_SRCS:
         obj = os.path.join(OBJ_DIR, src + ".o")
-        sdeps = deps if src.endswith(".hip") else [os.path.join(CSRC, d) for d in [src] + HOST_DEPS]
+        if src.endswith(".hip"):
+            # each kernel file sees the headers, not the other sources: a change
+            # to one leaves the other's object (and code objects) as they are
+            sdeps = [d for d in deps if not d.endswith((".hip", ".cpp")) or d.endswith(src)]
+        else:
+            sdeps = [os.path.join(CSRC, d) for d in [src] + HOST_DEPS]
         if force or _stale(obj, sdeps):
             _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", "-o", obj,
                   os.path.join(CSRC, src)])
@@ -85,6 +92,15 @@ def build_product(force=False, extra_flags=(), variant="variant"):
 def build_hostemu(force=False):
     out = os.path.join(ROOT, "tests", "native", "libhostemu.so")
     src = os.path.join(ROOT, "tests", "native", "hostemu.cpp")
+    deps = [src] + [os.path.join(CSRC, d) for d in PRODUCT_DEPS]
+    if force or _stale(out, deps):
+        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
+    return out
+
+
+def build_hostemu_keyset(force=False):
+    out = os.path.join(ROOT, "tests", "native", "libhostemu_keyset.so")
+    src = os.path.join(ROOT, "tests", "native", "hostemu_keyset.cpp")
     deps = [src] + [os.path.join(CSRC, d) for d in PRODUCT_DEPS]
     if force or _stale(out, deps):
         _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
@@ -109,8 +125,9 @@ def main(argv=None):
     # the product and the host harness are independent single-threaded
     # compiles of the same device code: run them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force)]
+    with ThreadPoolExecutor(max_workers=3) as ex:
+        jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force),
+                ex.submit(build_hostemu_keyset, force)]
         for j in jobs:
             j.result()
     build_oracle()

@@ -33,11 +33,13 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 
 #include "../../include/stl.h"
 #include "stl_kernels.h"
+#include "stl_keyset.h"
 
 namespace {
 
@@ -1364,6 +1366,49 @@ int env_int(const char* name, int dflt) {
 
 }  // namespace
 
+// ---- registered signer sets (stl_keyset_*) ----
+// One keyset: the keys (host), their first-index map, and on one device the
+// records and tables of its nkeys keys plus the base point's (stl_keyset.h).
+struct stl_keyset {
+  int ordinal = -1;
+  uint32_t nkeys = 0;
+  std::vector<uint8_t> pk;
+  std::map<std::array<uint8_t, 32>, uint32_t> first;
+  DevBuf rec, tables;
+  size_t table_bytes() const { return ((size_t)nkeys + 1) * stl::keyset_key_words() * 4; }
+  const uint32_t* d_rec() const { return static_cast<const uint32_t*>(rec.p); }
+  const uint32_t* d_tables() const { return static_cast<const uint32_t*>(tables.p); }
+};
+
+namespace {
+// The live keysets.  g_ks_mu is held while a call looks its handle up and
+// enqueues its kernels, and while a keyset is destroyed -- so a handle that
+// passed the lookup stays alive until its work is on the stream, and destroy
+// (which then waits for the device) sees all of it.  Lock order: g_ks_mu
+// before g_mu / a device's mu / a stream context's mu.
+std::mutex g_ks_mu;
+std::set<const stl_keyset*> g_keysets;
+
+// Waits for the device, then frees the keyset (g_ks_mu held, ks registered).
+void keyset_free_locked(stl_keyset* ks) {
+  g_keysets.erase(ks);
+  DeviceGuard guard;
+  if (hipSetDevice(ks->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
+  ks->rec.release();
+  ks->tables.release();
+  delete ks;
+}
+
+void keysets_release_all() {
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  while (!g_keysets.empty()) keyset_free_locked(const_cast<stl_keyset*>(*g_keysets.begin()));
+}
+
+int check_keyset_flags(uint32_t flags) {
+  return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_DEBUG_RAW_PREDICATE)) ? STL_EINVAL : STL_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int stl_init(const stl_config* cfg) {
@@ -1462,6 +1507,7 @@ int stl_init(const stl_config* cfg) {
 
 void stl_shutdown(void) {
   stl_comm_destroy();
+  keysets_release_all();
   DeviceGuard guard;
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto& d : g_devs) {
@@ -1479,7 +1525,7 @@ int stl_device_count(void) {
   return (int)g_devs.size();
 }
 
-const char* stl_version(void) { return "stl 0.2.0 (gfx950, abi 2)"; }
+const char* stl_version(void) { return "stl 0.3.0 (gfx950, abi 4)"; }
 
 const char* stl_strerror(int rc) {
   switch (rc) {
@@ -2370,6 +2416,217 @@ int stl_bitmap_gatherv_device(const uint64_t* d_words, size_t nwords, uint64_t* 
   const int erc = rccl_settle(g_pcomm, g_rccl.GroupEnd());
   if (erc) pcomm_abort_locked();  // failed or timed out: the communicator is unusable
   return rc ? rc : erc;
+}
+
+// ---- registered signer sets ----
+namespace {
+// B's encoding (y = 4/5, x positive): the base point's table is built by the
+// keys' kernels from it
+void base_point_bytes(uint8_t out[32]) {
+  std::memset(out, 0x66, 32);
+  out[0] = 0x58;
+}
+
+// Decodes the keys and builds the tables of `ks` on d.stream (d.mu held).
+// `all` (the keys and B's encoding, the copy's source), dpk and scratch are
+// the caller's: they outlive the stream's work also when a call here fails.
+int keyset_build(Device& d, stl_keyset& ks, std::vector<uint8_t>& all, DevBuf& dpk, DevBuf& scratch) {
+  const uint32_t nk = ks.nkeys;
+  STL_TRY(hipSetDevice(d.ordinal));
+  STL_RC(ks.rec.ensure(((size_t)nk + 1) * stl::keyset_rec_words() * 4));
+  STL_RC(ks.tables.ensure(ks.table_bytes()));
+  STL_RC(dpk.ensure(((size_t)nk + 1) * 32));
+  // the build runs `step` keys at a time: the normalisation's scratch stays small
+  const uint32_t step = std::min<uint32_t>(nk + 1, 512);
+  STL_RC(scratch.ensure((size_t)step * stl::keyset_scratch_words_per_key() * 4));
+  all = ks.pk;
+  all.resize(((size_t)nk + 1) * 32);
+  base_point_bytes(&all[(size_t)nk * 32]);
+  STL_TRY(hipMemcpyAsync(dpk.p, all.data(), all.size(), hipMemcpyHostToDevice, d.stream));
+  STL_TRY(hipMemsetAsync(ks.tables.p, 0, ks.table_bytes(), d.stream));
+  STL_TRY(stl::launch_keyset_decode(static_cast<const uint8_t*>(dpk.p), nk, static_cast<uint32_t*>(ks.rec.p), d.stream));
+  for (uint32_t first = 0; first <= nk; first += step)
+    STL_TRY(stl::launch_keyset_build(ks.d_rec(), first, std::min<uint32_t>(step, nk + 1 - first),
+                                     static_cast<uint32_t*>(ks.tables.p), static_cast<uint32_t*>(scratch.p),
+                                     d.stream));
+  STL_TRY(hipStreamSynchronize(d.stream));
+  return STL_OK;
+}
+
+// The live keyset of a handle on the calling thread's device (g_ks_mu held).
+int keyset_for_call(const stl_keyset* ks, Device** d) {
+  if (!ks || !g_keysets.count(ks)) return STL_EINVAL;
+  STL_RC(device_for_call(d));
+  return (*d)->ordinal == ks->ordinal ? STL_OK : STL_EINVAL;
+}
+
+int keyset_launch(Device& d, const stl_keyset& ks, const uint32_t* d_key_index, const uint8_t* d_sig,
+                  const uint8_t* d_msg, size_t n, uint64_t* d_words, uint32_t flags, hipStream_t s) {
+  STL_TRY(stl::launch_keyset_verify(d_sig, d_msg, d_key_index, (uint32_t)n, ks.d_rec(), ks.d_tables(), ks.nkeys,
+                                    stl::core_policy(stl::kernel_mode(flags)), d_words, dev_counters(d), s));
+  return STL_OK;
+}
+}  // namespace
+
+int stl_keyset_create(const uint8_t* pk, size_t nkeys, uint32_t flags, stl_keyset** out) {
+  if (out) *out = nullptr;
+  if (!pk || !out || nkeys == 0 || nkeys > STL_KEYSET_MAX_KEYS || flags != 0) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  std::unique_ptr<stl_keyset> ks(new stl_keyset());
+  ks->ordinal = d->ordinal;
+  ks->nkeys = (uint32_t)nkeys;
+  ks->pk.assign(pk, pk + nkeys * 32);
+  for (size_t i = 0; i < nkeys; ++i) {
+    std::array<uint8_t, 32> a;
+    std::memcpy(a.data(), pk + 32 * i, 32);
+    ks->first.emplace(a, (uint32_t)i);  // keeps the first index of a duplicate
+  }
+  DeviceGuard guard;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(d->mu);
+    DevBuf dpk, scratch;
+    std::vector<uint8_t> all;
+    rc = keyset_build(*d, *ks, all, dpk, scratch);
+    if (rc) (void)hipStreamSynchronize(d->stream);  // nothing may still run on the buffers freed below
+    dpk.release();
+    scratch.release();
+    if (rc) {
+      ks->rec.release();
+      ks->tables.release();
+    }
+  }
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  g_keysets.insert(ks.get());
+  *out = ks.release();
+  return STL_OK;
+}
+
+void stl_keyset_destroy(stl_keyset* ks) {
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  if (ks && g_keysets.count(ks)) keyset_free_locked(ks);
+}
+
+int stl_keyset_get_info(const stl_keyset* ks, stl_keyset_info* out) {
+  if (!out || out->struct_size != sizeof(stl_keyset_info)) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  if (!ks || !g_keysets.count(ks)) return STL_EINVAL;
+  const stl::KeysetGeometry g = stl::keyset_geometry();
+  out->nkeys = ks->nkeys;
+  out->window_bits = g.window_bits;
+  out->windows = g.windows;
+  out->rows_per_window = g.rows_per_window;
+  out->row_bytes = g.row_bytes;
+  out->device = ks->ordinal;
+  out->reserved = 0;
+  out->table_bytes = ks->table_bytes();
+  return STL_OK;
+}
+
+long long stl_keyset_find(const stl_keyset* ks, const uint8_t pk[32]) {
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  if (!ks || !pk || !g_keysets.count(ks)) return -1;
+  std::array<uint8_t, 32> a;
+  std::memcpy(a.data(), pk, 32);
+  const auto it = ks->first.find(a);
+  return it == ks->first.end() ? -1 : (long long)it->second;
+}
+
+int stl_keyset_verify_batch_device(stl_keyset* ks, const uint32_t* d_key_index, const uint8_t* d_sig,
+                                   const uint8_t* d_msg, size_t n, uint64_t* d_bitmap_words, uint32_t flags,
+                                   void* stream) {
+  if (!ks) return STL_EINVAL;
+  STL_RC(check_keyset_flags(flags));
+  if (n > 0xffffffc0ull || (n && (!d_key_index || !d_sig || !d_msg || !d_bitmap_words))) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  Device* d = nullptr;
+  STL_RC(keyset_for_call(ks, &d));
+  if (n == 0) return STL_OK;
+  return keyset_launch(*d, *ks, d_key_index, d_sig, d_msg, n, d_bitmap_words, flags, static_cast<hipStream_t>(stream));
+}
+
+int stl_keyset_tx_verify_batch_device(stl_keyset* ks, const uint32_t* d_key_index, const uint8_t* d_preimages,
+                                      const uint64_t* d_offset, const uint32_t* d_len, const uint8_t* d_sig, size_t n,
+                                      uint64_t* d_bitmap_words, uint32_t flags, void* stream) {
+  if (!ks) return STL_EINVAL;
+  STL_RC(check_keyset_flags(flags));
+  if (n > 0xffffffc0ull ||
+      (n && (!d_key_index || !d_preimages || !d_offset || !d_len || !d_sig || !d_bitmap_words)))
+    return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  Device* d = nullptr;
+  STL_RC(keyset_for_call(ks, &d));
+  if (n == 0) return STL_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const std::shared_ptr<StreamCtx> c = stream_ctx(*d, s);
+  std::lock_guard<std::mutex> cl(c->mu);
+  uint32_t* ctr = nullptr;
+  STL_RC(ctx_queue(*c, n, &ctr));
+  STL_RC(c->scratch.ensure(n * 32));  // the signing hashes
+  uint8_t* msg = static_cast<uint8_t*>(c->scratch.p);
+  STL_TRY(stl::launch_tx_hash(d_preimages, d_offset, d_len, (uint32_t)n, msg, ctr, hash_grid(*d), s,
+                              hash_long_min(*d, n)));
+  return keyset_launch(*d, *ks, d_key_index, d_sig, msg, n, d_bitmap_words, flags, s);
+}
+
+int stl_keyset_verify_batch(stl_keyset* ks, const uint32_t* key_index, const uint8_t* sig, const uint8_t* msg,
+                            size_t n, uint8_t* accept_bitmap, uint32_t flags) {
+  if (!ks) return STL_EINVAL;
+  STL_RC(check_keyset_flags(flags));
+  if (n > 0xffffffc0ull || (n && (!key_index || !sig || !msg || !accept_bitmap))) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  Device* dp = nullptr;
+  STL_RC(keyset_for_call(ks, &dp));
+  if (n == 0) return STL_OK;
+  for (size_t i = 0; i < n; ++i)
+    if (key_index[i] >= ks->nkeys) return STL_EINVAL;
+  CallSpan span{"stl_keyset_verify_batch", n};
+  Device& d = *dp;
+  std::lock_guard<std::mutex> dl(d.mu);
+  const size_t words = (n + 63) / 64;
+  std::vector<uint64_t> host_words(words);
+  auto go = [&]() -> int {
+    STL_RC(d.sig.ensure(n * 64));
+    STL_RC(d.msg.ensure(n * 32));
+    STL_RC(d.len.ensure(n * 4));
+    STL_RC(d.bitmap.ensure(words * 8));
+    STL_TRY(hipMemcpyAsync(d.sig.p, sig, n * 64, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.msg.p, msg, n * 32, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.len.p, key_index, n * 4, hipMemcpyHostToDevice, d.stream));
+    STL_RC(keyset_launch(d, *ks, static_cast<const uint32_t*>(d.len.p), static_cast<const uint8_t*>(d.sig.p),
+                         static_cast<const uint8_t*>(d.msg.p), n, static_cast<uint64_t*>(d.bitmap.p), flags, d.stream));
+    STL_TRY(hipMemcpyAsync(host_words.data(), d.bitmap.p, words * 8, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {  // nothing may still read the caller's rows or write host_words
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  std::memcpy(accept_bitmap, host_words.data(), (n + 7) / 8);
+  return span.finish(STL_OK);
+}
+
+int stl_debug_keyset_rows(const stl_keyset* ks, uint32_t key, uint32_t first_row, uint32_t nrows,
+                          uint32_t* out_words) {
+  if (!out_words) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ks_mu);
+  Device* d = nullptr;
+  STL_RC(keyset_for_call(ks, &d));
+  const stl::KeysetGeometry g = stl::keyset_geometry();
+  const uint64_t rows = (uint64_t)g.windows * g.rows_per_window;
+  if (key == STL_KEYSET_BASE) key = ks->nkeys;
+  else if (key >= ks->nkeys) return STL_EINVAL;
+  if ((uint64_t)first_row + nrows > rows) return STL_EINVAL;
+  if (nrows == 0) return STL_OK;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(ks->d_tables()) +
+                       ((size_t)key * rows + first_row) * g.row_bytes;
+  STL_TRY(hipDeviceSynchronize());
+  STL_TRY(hipMemcpy(out_words, src, (size_t)nrows * g.row_bytes, hipMemcpyDeviceToHost));
+  return STL_OK;
 }
 
 }  // extern "C"

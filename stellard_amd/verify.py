@@ -398,6 +398,124 @@ def tx_blob_prepare_device(blobs, offsets, lengths, tx_ids=True, stream=None, ki
     return out
 
 
+# ---- registered signer sets (stl_keyset_*) ----
+
+class KeysetInfo(ctypes.Structure):
+    """stl_keyset_info (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("nkeys", ctypes.c_uint32), ("window_bits", ctypes.c_uint32),
+                ("windows", ctypes.c_uint32), ("rows_per_window", ctypes.c_uint32), ("row_bytes", ctypes.c_uint32),
+                ("device", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64)]
+
+
+class Keyset:
+    """A registered signer set (stl_keyset_create): per-key comb tables on the
+    current device, verified against by key index -- 64 table additions per
+    signature, no doubling, the same bits as the per-signature calls.
+
+        with Keyset(pks) as ks:
+            words = ks.verify_batch_device(key_index, sig, msg)
+    """
+
+    def __init__(self, pks):
+        pks = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 32)
+        h = ctypes.c_void_p()
+        N.check(N.load().stl_keyset_create(_buf(pks), pks.shape[0], 0, ctypes.byref(h)), "stl_keyset_create")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            N.load().stl_keyset_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        i = KeysetInfo(struct_size=ctypes.sizeof(KeysetInfo))
+        N.check(N.load().stl_keyset_get_info(self._h, ctypes.byref(i)), "stl_keyset_get_info")
+        return {k: getattr(i, k) for k, _ in KeysetInfo._fields_ if k not in ("struct_size", "reserved")}
+
+    def find(self, pk):
+        """First index of the 32-byte key, or -1."""
+        pk = bytes(pk)
+        if len(pk) != 32:
+            raise ValueError("a key is 32 bytes")
+        return int(N.load().stl_keyset_find(self._h, pk))
+
+    def verify_batch(self, key_index, sig, msg, policy=POLICY_SODIUM_1_0_18):
+        """Host arrays -> bool[n]; an index >= nkeys raises StlError(STL_EINVAL)."""
+        key_index = np.ascontiguousarray(key_index, dtype=np.uint32).reshape(-1)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        msg = np.ascontiguousarray(msg, dtype=np.uint8).reshape(-1, 32)
+        n = sig.shape[0]
+        if msg.shape[0] != n or key_index.shape[0] != n:
+            raise ValueError("key_index/sig/msg batch sizes differ")
+        bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+        N.check(N.load().stl_keyset_verify_batch(self._h, _buf(key_index), _buf(sig), _buf(msg), n, _buf(bitmap),
+                                                 policy), "stl_keyset_verify_batch")
+        return unpack_bitmap(bitmap, n)
+
+    @staticmethod
+    def _device_rows(key_index, *ts):
+        import torch
+        for t in (key_index,) + ts:
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        if key_index.dtype != torch.int32:
+            raise ValueError("key_index must be int32 (the bits of a uint32 index)")
+
+    def verify_batch_device(self, key_index, sig, msg, out_words=None, policy=POLICY_SODIUM_1_0_18, stream=None):
+        """key_index (n,) int32 / sig (n,64) / msg (n,32) CUDA tensors -> int64
+        bitmap words (async on ``stream``); a row whose index is >= nkeys gets
+        bit 0."""
+        import torch
+        n = sig.shape[0]
+        if out_words is None:
+            out_words = torch.empty((n + 63) // 64, dtype=torch.int64, device=sig.device)
+        self._device_rows(key_index, sig, msg, out_words)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        N.check(N.load().stl_keyset_verify_batch_device(self._h, p(key_index), p(sig), p(msg), n, p(out_words), policy,
+                                                        _stream_ptr(stream)), "stl_keyset_verify_batch_device")
+        return out_words
+
+    def tx_verify_batch_device(self, key_index, preimages, offsets, lengths, sig, out_words=None,
+                               policy=POLICY_SODIUM_1_0_18, stream=None):
+        """checkSign / validation form: SHA512Half of each preimage, then the
+        keyset verify (same bits as tx_hash_batch_device + verify_batch_device)."""
+        import torch
+        n = offsets.shape[0]
+        if out_words is None:
+            out_words = torch.empty(((n + 63) // 64,), dtype=torch.int64, device=preimages.device)
+        self._device_rows(key_index, sig, out_words)
+        _check_rows(preimages, offsets, lengths)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        N.check(N.load().stl_keyset_tx_verify_batch_device(
+            self._h, p(key_index), p(preimages), p(offsets), p(lengths), p(sig), n, p(out_words), policy,
+            _stream_ptr(stream)), "stl_keyset_tx_verify_batch_device")
+        return out_words
+
+    def rows(self, key, first_row, nrows):
+        """Test hook (stl_debug_keyset_rows): table rows of key ``key``
+        (N.STL_KEYSET_BASE: the base point's) -> uint32[nrows, row_bytes / 4]."""
+        words = self.info()["row_bytes"] // 4
+        out = np.zeros((nrows, words), dtype=np.uint32)
+        N.check(N.load().stl_debug_keyset_rows(self._h, key, first_row, nrows, _buf(out)), "stl_debug_keyset_rows")
+        return out
+
+
 class Batcher:
     """stl_batcher (include/stl.h): single requests from any thread, run as
     device batches by max_batch / max_delay_us; ``submit`` / ``submit_tx``
