@@ -516,7 +516,14 @@ int stl_debug_sign_adversarial_device(const uint8_t *d_seed, const uint8_t *d_ms
  * encode([S]B + [k](-A)) == R, the predicate of the per-signature calls bit
  * for bit (the table is built on the decoded point itself, so mixed-order,
  * small-order, non-canonical and undecodable keys answer as they do there
- * under the call's policy).  A row names its signer by its index in the set.
+ * under the call's policy).  A row names its signer by its index in the set,
+ * or -- the *_by_key calls and stl_keyset_lookup_device -- by its 32-byte
+ * public key: the keyset carries a key -> index hash map on the device (first
+ * index of a duplicate, as stl_keyset_find; at most 64 KiB, not counted in
+ * table_bytes), and a by-key call verifies the rows of registered signers from
+ * the tables and every other row with the per-signature kernels, so its bits
+ * equal stl_ed25519_verify_batch_device's on every input: the set need not be
+ * closed (signers funded after registration, validations from outside the UNL).
  * A keyset lives on one device (the calling thread's current device at
  * creation; the multi-GPU sharding of the host batch calls does not apply) and
  * holds table_bytes of device memory: 512 KiB per key plus the base table. */
@@ -560,6 +567,40 @@ int stl_keyset_verify_batch_device(stl_keyset *ks, const uint32_t *d_key_index, 
 int stl_keyset_tx_verify_batch_device(stl_keyset *ks, const uint32_t *d_key_index, const uint8_t *d_preimages,
                                       const uint64_t *d_offset, const uint32_t *d_len, const uint8_t *d_sig,
                                       size_t n, uint64_t *d_bitmap_words, uint32_t flags, void *stream);
+/* ---- keysets by public key ----
+ * Key index of every row's key: d_key_index[i] = the first index of d_pk[32 i ..] in the set, or
+ * STL_KEYSET_NOT_FOUND.  Asynchronous on `stream`; device memory, d_pk 16-byte aligned.
+ * d_miss_count (nullable): one uint32 in device memory, set to the number of rows not found.
+ * Followed by stl_keyset_verify_batch_device on the same stream this is the fully asynchronous
+ * closed-set check: a row of an unregistered signer gets accept bit 0. */
+#define STL_KEYSET_NOT_FOUND 0xFFFFFFFFu
+int stl_keyset_lookup_device(stl_keyset *ks, const uint8_t *d_pk, size_t n, uint32_t *d_key_index,
+                             uint32_t *d_miss_count, void *stream);
+/* Open-set verify: row i is (d_pk[32 i..], d_sig[64 i..], d_msg[32 i..]), all 16-byte aligned; the
+ * bits of stl_ed25519_verify_batch_device(d_sig, d_msg, d_pk, ...) under the same policy, for every
+ * input.  Rows whose key is registered are verified from the tables; the others ("misses") are
+ * gathered, verified by the per-signature kernels and their bits put back.  flags as
+ * stl_keyset_verify_batch_device.  *misses (nullable): the number of rows of unregistered signers.
+ * SYNCHRONISATION: the call waits once on `stream`, for its lookup kernel (an event recorded behind
+ * it) -- the host has to learn the miss count before it can size and launch the per-signature
+ * kernels.  The keyset verify of all n rows is enqueued before that wait and runs during it;
+ * everything else is asynchronous, and the bitmap is complete when `stream` reaches the call's end.
+ * The stream context holds the call's buffers: 8 B per row, 128 B per miss. */
+int stl_keyset_verify_by_key_device(stl_keyset *ks, const uint8_t *d_pk, const uint8_t *d_sig,
+                                    const uint8_t *d_msg, size_t n, uint64_t *d_bitmap_words, uint32_t flags,
+                                    void *stream, size_t *misses);
+/* Host form: host memory, synchronous (uploads on the device's stream, then the device path). */
+int stl_keyset_verify_by_key(stl_keyset *ks, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg, size_t n,
+                             uint8_t *accept_bitmap, uint32_t flags);
+/* Serialized validations / transactions in device memory (the UNL-validation and ledger-close
+ * binding): the pass of stl_signed_blob_prepare_device into the stream context (128 B per row), then
+ * the by-key verify on each row's SigningPubKey.  Bits, d_status and d_id (nullable) as
+ * stl_signed_blob_verify_batch_device writes them; synchronisation and *misses as
+ * stl_keyset_verify_by_key_device. */
+int stl_keyset_signed_blob_verify_batch_device(stl_keyset *ks, uint32_t kind, const uint8_t *d_blobs,
+                                               const uint64_t *d_offset, const uint32_t *d_len, size_t n,
+                                               uint64_t *d_bitmap_words, uint8_t *d_status, uint8_t *d_id,
+                                               uint32_t flags, void *stream, size_t *misses);
 /* Test hook: nrows table rows from first_row (row = w * rows_per_window + j - 1) of key `key`
  * (STL_KEYSET_BASE: the base point's table) copied to host memory, row_bytes / 4 words each. */
 int stl_debug_keyset_rows(const stl_keyset *ks, uint32_t key, uint32_t first_row, uint32_t nrows,

@@ -38,6 +38,7 @@ STL_DEBUG_RAW_PREDICATE = 0x80000000  # test-only: no S < L (stl.h)
 # registered signer sets (stl_keyset_*)
 STL_KEYSET_MAX_KEYS = 4096
 STL_KEYSET_BASE = 0xFFFFFFFF
+STL_KEYSET_NOT_FOUND = 0xFFFFFFFF
 
 # stl_debug_tuning keys
 STL_TUNE_FUSED_PREP = 0
@@ -125,6 +126,12 @@ SYMBOLS = [
     ("stl_keyset_tx_verify_batch_device", ctypes.c_int,
      [_P, _P, _U8P, _P, _P, _U8P, ctypes.c_size_t, _P, ctypes.c_uint32, _P]),
     ("stl_debug_keyset_rows", ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P]),
+    ("stl_keyset_lookup_device", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _P, _P, _P]),
+    ("stl_keyset_verify_by_key_device", ctypes.c_int,
+     [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _P, ctypes.c_uint32, _P, _P]),
+    ("stl_keyset_verify_by_key", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, ctypes.c_uint32]),
+    ("stl_keyset_signed_blob_verify_batch_device", ctypes.c_int,
+     [_P, ctypes.c_uint32, _U8P, _P, _P, ctypes.c_size_t, _P, _U8P, _U8P, ctypes.c_uint32, _P, _P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -4,6 +4,7 @@
   tests/native/libhostemu.so     test harness: the device verify code compiled
                                  for the host (bound checks on)
   tests/native/libhostemu_keyset.so  the same for the keyset's comb code
+  tests/native/libhostemu_keyset_map.so  the keyset's key -> index map
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -22,7 +23,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_api.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
-                               "stl_comb.h", "stl_keyset.h",
+                               "stl_comb.h", "stl_keyset.h", "stl_keyset_map.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
 
@@ -53,7 +54,7 @@ def _run(cmd, cwd=ROOT):
 # per-object dependencies: the host sources see only the ABI header and the
 # launcher declarations, so a host-side change does not recompile the kernels
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
-HOST_DEPS = ["stl_kernels.h", "stl_keyset.h", os.path.join("..", "..", "include", "stl.h")]
+HOST_DEPS = ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -107,6 +108,15 @@ def build_hostemu_keyset(force=False):
     return out
 
 
+def build_hostemu_keyset_map(force=False):
+    out = os.path.join(ROOT, "tests", "native", "libhostemu_keyset_map.so")
+    src = os.path.join(ROOT, "tests", "native", "hostemu_keyset_map.cpp")
+    deps = [src, os.path.join(CSRC, "stl_keyset_map.h")]
+    if force or _stale(out, deps):
+        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
+    return out
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -125,9 +135,9 @@ def main(argv=None):
     # the product and the host harness are independent single-threaded
     # compiles of the same device code: run them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=3) as ex:
+    with ThreadPoolExecutor(max_workers=4) as ex:
         jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force),
-                ex.submit(build_hostemu_keyset, force)]
+                ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force)]
         for j in jobs:
             j.result()
     build_oracle()

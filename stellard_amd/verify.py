@@ -507,6 +507,99 @@ class Keyset:
             _stream_ptr(stream)), "stl_keyset_tx_verify_batch_device")
         return out_words
 
+    # ---- by public key: the set need not be closed ----
+
+    @staticmethod
+    def _device_keys(*ts):
+        import torch
+        for t in ts:
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        for t in ts[:3]:
+            if t is not None and t.dtype != torch.uint8:
+                raise ValueError("pk / sig / msg must be uint8")
+
+    def lookup_device(self, pk, out_index=None, miss_count=None, stream=None):
+        """pk (n,32) uint8 CUDA tensor -> int32[n] key indices (the bits of
+        uint32; N.STL_KEYSET_NOT_FOUND, i.e. -1, for a key that is not in the
+        set), async on ``stream``.  ``miss_count``: an int32 CUDA tensor whose
+        first element receives the number of rows not found."""
+        import torch
+        n = pk.shape[0]
+        if out_index is None:
+            out_index = torch.empty(n, dtype=torch.int32, device=pk.device)
+        self._device_keys(pk, None, None, out_index, miss_count)
+        if out_index.dtype != torch.int32 or out_index.numel() < n:
+            raise ValueError("out_index must be int32, one element per row")
+        if miss_count is not None and (miss_count.dtype != torch.int32 or miss_count.numel() < 1):
+            raise ValueError("miss_count must be an int32 tensor")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_keyset_lookup_device(self._h, p(pk), n, p(out_index), p(miss_count),
+                                                  _stream_ptr(stream)), "stl_keyset_lookup_device")
+        return out_index
+
+    def verify_by_key_device(self, pk, sig, msg, out_words=None, policy=POLICY_SODIUM_1_0_18, stream=None):
+        """pk (n,32) / sig (n,64) / msg (n,32) CUDA tensors -> (int64 bitmap
+        words, misses): the bits of verify_batch_device(sig, msg, pk);
+        registered signers from the tables, the ``misses`` other rows through
+        the per-signature kernels.  Waits once on ``stream`` (for the lookup);
+        the words are complete when ``stream`` reaches the call's end."""
+        import torch
+        n = sig.shape[0]
+        if out_words is None:
+            out_words = torch.empty((n + 63) // 64, dtype=torch.int64, device=sig.device)
+        self._device_keys(pk, sig, msg, out_words)
+        if pk.shape[0] != n or msg.shape[0] != n:
+            raise ValueError("pk/sig/msg batch sizes differ")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        misses = ctypes.c_size_t(0)
+        N.check(N.load().stl_keyset_verify_by_key_device(self._h, p(pk), p(sig), p(msg), n, p(out_words), policy,
+                                                         _stream_ptr(stream), ctypes.byref(misses)),
+                "stl_keyset_verify_by_key_device")
+        return out_words, int(misses.value)
+
+    def verify_by_key(self, pk, sig, msg, policy=POLICY_SODIUM_1_0_18):
+        """Host arrays -> bool[n] (the bits of verify_batch(sig, msg, pk))."""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, 32)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        msg = np.ascontiguousarray(msg, dtype=np.uint8).reshape(-1, 32)
+        n = sig.shape[0]
+        if msg.shape[0] != n or pk.shape[0] != n:
+            raise ValueError("pk/sig/msg batch sizes differ")
+        bitmap = np.zeros((n + 7) // 8, dtype=np.uint8)
+        N.check(N.load().stl_keyset_verify_by_key(self._h, _buf(pk), _buf(sig), _buf(msg), n, _buf(bitmap), policy),
+                "stl_keyset_verify_by_key")
+        return unpack_bitmap(bitmap, n)
+
+    def signed_blob_verify_batch_device(self, blobs, offsets, lengths, out_words=None, tx_ids=False,
+                                        policy=POLICY_SODIUM_1_0_18, stream=None, kind=None, out_status=None,
+                                        out_ids=None):
+        """Serialized validations / transactions in HBM, verified by each
+        row's SigningPubKey against the set -> dict of words, status, tx_id (as
+        verify.signed_blob_verify_batch_device) and misses."""
+        import torch
+        n = offsets.shape[0]
+        dev = blobs.device
+        if out_words is None:
+            out_words = torch.empty(((n + 63) // 64,), dtype=torch.int64, device=dev)
+        status = torch.empty((n,), dtype=torch.uint8, device=dev) if out_status is None else out_status
+        tx_id = out_ids if out_ids is not None else (torch.empty((n, 32), dtype=torch.uint8, device=dev)
+                                                     if tx_ids else None)
+        if status.dtype != torch.uint8 or (tx_id is not None and tx_id.dtype != torch.uint8):
+            raise ValueError("out_status / out_ids must be torch.uint8")
+        if tx_id is not None and tx_id.dim() > 1 and tx_id.shape[-1] != 32:
+            raise ValueError("out_ids must be (n, 32) bytes")
+        if status.numel() < n or (tx_id is not None and tx_id.numel() < 32 * n):
+            raise ValueError("status / id buffers smaller than the batch")
+        _check_rows(blobs, offsets, lengths, out_words, status, tx_id)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        misses = ctypes.c_size_t(0)
+        N.check(N.load().stl_keyset_signed_blob_verify_batch_device(
+            self._h, N.STL_BLOB_TRANSACTION if kind is None else kind, p(blobs), p(offsets), p(lengths), n,
+            p(out_words), p(status), p(tx_id), policy, _stream_ptr(stream), ctypes.byref(misses)),
+            "stl_keyset_signed_blob_verify_batch_device")
+        return {"words": out_words, "status": status, "tx_id": tx_id, "misses": int(misses.value)}
+
     def rows(self, key, first_row, nrows):
         """Test hook (stl_debug_keyset_rows): table rows of key ``key``
         (N.STL_KEYSET_BASE: the base point's) -> uint32[nrows, row_bytes / 4]."""

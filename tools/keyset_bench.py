@@ -18,6 +18,9 @@ anything else is started.  Prints one JSON line (kept as
 profiles/keyset/bench.json).
 
     python3 tools/keyset_bench.py [--rows N] [--rounds R] [--step-timeout S] [--out FILE]
+
+With --by-key the tool measures the calls that take public keys instead (see
+by_key below; kept as profiles/keyset/by_key.json).
 """
 import argparse
 import json
@@ -45,6 +48,94 @@ def spread(ms):
             "max_ms": round(float(a.max()), 4), "calls": int(a.size)}
 
 
+def by_key(args, out, step, timed, V, torch, keys_all, who, pk, sig, msg, s):
+    """--by-key: the same S signers x rows, five legs alternating a b c d e e d c b a:
+
+        a  Keyset.verify_batch_device            indices given
+        b  Keyset.verify_by_key_device           every signer registered (0 misses)
+        c  Keyset.verify_by_key_device           one signer in 16 left out of the set
+        d  Keyset.verify_by_key_device           none of the signers registered
+        e  verify_batch_device                   the per-signature call, automatic choice
+
+    All legs verify the same rows, so their bits are compared directly before
+    timing.  Also timed, outside the alternation: the lookup kernel alone
+    (lookup_device), which with the call's one wait is what b adds to a."""
+    n, S = sig.shape[0], args.signers
+    dev = sig.device
+    out["tool"] = "keyset_bench --by-key"
+    keys = keys_all[:S].cpu().numpy()
+    keep = np.arange(S) % 16 != 0
+    others = keys_all[S:2 * S].cpu().numpy() if keys_all.shape[0] >= 2 * S else keys_all[S:].cpu().numpy()
+    sets = step("create", lambda: {"all": V.Keyset(keys), "most": V.Keyset(keys[keep]), "none": V.Keyset(others)})
+    words = {k: torch.empty((n + 63) // 64, dtype=torch.int64, device=dev) for k in "abcde"}
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    misses = {}
+
+    def by(name, leg):
+        def fn():
+            misses[leg] = sets[name].verify_by_key_device(pk, sig, msg, out_words=words[leg], stream=s)[1]
+        return fn
+    legs = {
+        "a_indexed": lambda: sets["all"].verify_batch_device(who, sig, msg, out_words=words["a"], stream=s),
+        "b_by_key_0_misses": by("all", "b"),
+        "c_by_key_1_in_16": by("most", "c"),
+        "d_by_key_all_misses": by("none", "d"),
+        "e_per_signature": lambda: V.verify_batch_device(sig, msg, pk, out_words=words["e"], stream=s),
+    }
+
+    def bits_equal():
+        for fn in legs.values():
+            fn()
+            fn()  # the automatic choice follows the previous call's sample
+        torch.cuda.synchronize()
+        exp = np.ones(n, dtype=bool)
+        exp[::16] = False
+        got = [V.words_to_bool(words[k], n) for k in "abcde"]
+        return bool(all(np.array_equal(g, exp) for g in got)), int(got[0].sum())
+    same, accepted = step("bits", bits_equal)
+    out["bits_equal"], out["accepted"] = same, accepted
+    out["misses"] = {"b": misses["b"], "c": misses["c"], "d": misses["d"]}
+    if not same or misses["b"] != 0 or misses["d"] != n or not 0 < misses["c"] < n // 8:
+        print(json.dumps(out))
+        print("the legs' bits or miss counts are wrong", file=sys.stderr)
+        sys.exit(1)
+
+    def ab():
+        ts = {k: [] for k in legs}
+        for k in legs:  # warm-up
+            legs[k]()
+            legs[k]()
+        torch.cuda.synchronize()
+        order = list(legs) + list(legs)[::-1]
+        for _ in range(args.rounds):
+            for k in order:
+                ts[k].append(timed(legs[k]))
+        return ts
+    ts = step("ab", ab)
+    out["legs"] = {k: spread(v) for k, v in ts.items()}
+    med = {k: v["median_ms"] for k, v in out["legs"].items()}
+    out["b_minus_a_ms"] = round(med["b_by_key_0_misses"] - med["a_indexed"], 4)
+    out["b_over_a"] = round(med["b_by_key_0_misses"] / med["a_indexed"], 4)
+    out["c_over_e"] = round(med["c_by_key_1_in_16"] / med["e_per_signature"], 4)
+    out["d_over_e"] = round(med["d_by_key_all_misses"] / med["e_per_signature"], 4)
+
+    def lookup_only():
+        fn = lambda: sets["all"].lookup_device(pk, out_index=idx, stream=s)  # noqa: E731
+        fn()
+        fn()
+        torch.cuda.synchronize()
+        return [timed(fn) for _ in range(2 * args.rounds)]
+    out["lookup_kernel"] = spread(step("lookup", lookup_only))
+    for ks in sets.values():
+        ks.close()
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 20)
@@ -52,6 +143,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--step-timeout", type=int, default=60)
     ap.add_argument("--out", default="")
+    ap.add_argument("--by-key", action="store_true", help="the by-key legs (kept as profiles/keyset/by_key.json)")
     args = ap.parse_args()
     if args.rounds < 10:
         ap.error("--rounds >= 10 (20 timed calls per leg)")
@@ -109,6 +201,9 @@ def main():
     # ---- the signer shape of configs[0] / configs[4]: S signers x rows ----
     S = args.signers
     who, pk, sig = step("rows", lambda: rows_for(S))
+    if args.by_key:
+        by_key(args, out, step, timed, V, torch, keys_all, who, pk, sig, msg, s)
+        return
     creates = []
     for _ in range(3):
         ks, ms = step("create", lambda: make_keyset(S))
