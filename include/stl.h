@@ -405,6 +405,12 @@ typedef struct stl_stats {
    * themselves (STL_NO_AUTO_DEDUP above); a struct without this field
    * (struct_size = its offset) is accepted */
   uint64_t auto_dedup_chunks;
+  /* rows whose key's decoding came out of the decoded-key cache (checked
+   * against the row's key bytes before use) / rows that decoded their key and
+   * offered it to the cache (STL_TUNE_KEY_CACHE below); rows of paths that do
+   * not consult the cache count as neither.  A struct without these two
+   * fields (struct_size = the offset of the first) is accepted. */
+  uint64_t key_cache_hits, key_cache_misses;
 } stl_stats;
 int stl_get_stats(stl_stats *out);
 void stl_reset_stats(void);
@@ -470,9 +476,30 @@ int stl_debug_verify_k_device(const uint8_t *d_sig, const uint8_t *d_k, const ui
                                         kernel to overlap */
 #define STL_TUNE_RCCL_TIMEOUT_MS 7 /* 1..3,600,000 (default 120,000; env STL_RCCL_TIMEOUT_S): deadline of
                                       stl_comm_init_rank and stl_comm_sync */
+#define STL_TUNE_KEY_CACHE 13 /* 0..K (default K; 0 off): log2 of the sets in use of the decoded-key
+                                 cache, K being the log2 of the sets each device allocated at stl_init
+                                 (env STL_KEY_CACHE_LOG2: 10..24, default 20 = 256 MB per device; 0: no
+                                 cache).  Chunks that run one lane per signature without key dedup
+                                 look each row's key up in the cache -- 2^K sets of 6 slots {key tag,
+                                 x of the decoded -A}, kept from call to call -- and decode only the
+                                 keys they do not find, caching them.  A slot's x is used only after
+                                 the curve equation and the sign are checked against the row's own key
+                                 bytes, so whatever a slot holds the accept bits are those of a fresh
+                                 decoding.  A smaller value only masks the set index; entries left
+                                 from another value are harmless. */
 int stl_debug_tuning(int key, int value);
 /* Caller-stream contexts libstl currently keeps on the current device. */
 int stl_debug_stream_contexts(void);
+/* The current device's decoded-key cache.  _clear zeroes it (every slot
+ * empty) on the library's stream and waits for that; calls in flight on other
+ * streams are not waited for.  _info reports its device address, size in bytes
+ * (0: none), log2 of its sets and slots (ways) per set.  Set i is the 256
+ * bytes from byte 256 i: way w's 8-byte key tag at byte 8 w, the 32 canonical
+ * little-endian bytes of its x(-A) at byte 64 + 32 w (stl_keycache.h).  Tests
+ * write into it to show that no content changes an accept bit.  STL_ENODEV
+ * before stl_init. */
+int stl_debug_key_cache_clear(void);
+int stl_debug_key_cache_info(void **d_base, uint64_t *bytes, uint32_t *sets_log2, uint32_t *ways);
 /* Measurement only (bench.py clock_ghz): enqueues nwg one-wave workgroups on
  * `stream`; workgroup i writes d_out[4i..4i+3] = {shader cycle counter
  * (s_memtime), 100 MHz counter (s_memrealtime), XCC_ID register, HW_ID

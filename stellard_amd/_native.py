@@ -54,6 +54,7 @@ STL_TUNE_SHARED_KEYS = 9
 STL_TUNE_WIDE_MIN_ROWS = 10
 STL_TUNE_R_AHEAD = 11
 STL_TUNE_FIRST_CHUNK = 12
+STL_TUNE_KEY_CACHE = 13
 
 # per-transaction status of the serialized-transaction entry points
 STL_TX_OK = 0
@@ -112,6 +113,8 @@ SYMBOLS = [
     ("stl_debug_verify_k_device", ctypes.c_int, [_U8P, _U8P, _U8P, ctypes.c_size_t, _P, ctypes.c_uint32, _P]),
     ("stl_debug_tuning", ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     ("stl_debug_stream_contexts", ctypes.c_int, []),
+    ("stl_debug_key_cache_clear", ctypes.c_int, []),
+    ("stl_debug_key_cache_info", ctypes.c_int, [_P, _P, _P, _P]),
     ("stl_debug_clock_stamp", ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     ("stl_release_stream", ctypes.c_int, [_P]),
     ("stl_debug_sign_adversarial_device", ctypes.c_int,
@@ -158,7 +161,14 @@ def load():
             "(libstl has no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
     for name, res, args in SYMBOLS:
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # only an A/B build named by STL_LIB_PATH may predate an entry point
+            # (tools/gpujob.sh compares the product with an older build); the
+            # product itself exports every one
+            if os.environ.get("STL_LIB_PATH"):
+                continue
+            raise AttributeError(f"{LIB_PATH} does not export {name}")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

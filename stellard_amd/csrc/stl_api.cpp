@@ -39,6 +39,7 @@
 
 #include "../../include/stl.h"
 #include "stl_kernels.h"
+#include "stl_keycache.h"
 #include "stl_keyset.h"
 #include "stl_keyset_map.h"
 
@@ -285,6 +286,15 @@ std::atomic<int> g_tune_shared_keys{1}; // key dedup over several chunks: one ke
 std::atomic<int> g_tune_wide_min{0};    // key domains of fewer rows build no wide key tables (the 9-entry ones)
 std::atomic<int> g_tune_r_ahead{1};     // one-call checkSign with a shared key domain: R decoded ahead on its own stream
 std::atomic<int> g_tune_first_chunk{0}; // device-resident verify: rows of a smaller first chunk (0: equal chunks)
+// decoded-key cache (stl_keycache.h): log2 of the sets each device allocates
+// (env STL_KEY_CACHE_LOG2 at stl_init; 0: none) and of the sets in use
+// (STL_TUNE_KEY_CACHE; < 0: all that are allocated)
+std::atomic<int> g_key_cache_log2{stl::kKeyCacheLog2Default};
+std::atomic<int> g_tune_key_cache{-1};
+int key_cache_in_use() {
+  const int a = g_key_cache_log2.load(), t = g_tune_key_cache.load();
+  return t < 0 || t > a ? a : t;
+}
 
 // Rows per step of verify time: the device-resident verify runs a chunk's
 // 64-signature units on its resident waves, two per SIMD, so its time rises in
@@ -514,7 +524,12 @@ struct Device {
   ncclComm_t comm = nullptr;      // in-process communicator (rank = device index)
   std::mutex mu;
   DevBuf sig, msg, pk, bitmap, pre, off, len, ctr, ctr2, txid, status, wide, gather;
-  DevBuf counters;  // device u64 counters of stl_get_stats: [0] accepted, [1] full-length lanes
+  DevBuf counters;  // device u64 counters of stl_get_stats: [0] accepted, [1] full-length lanes,
+                    // [2] / [3] key-cache hits / misses
+  // the decoded-key cache (stl_keycache.h): allocated and zeroed once, in
+  // setup_device (never lazily: a call's memory use stays flat)
+  DevBuf key_cache;
+  int key_cache_log2 = 0;  // log2 of its sets; 0: none
   // workspace of every stream used: the pool streams' for good, at most
   // kMaxCallerStreams caller streams' (LRU)
   std::map<hipStream_t, std::shared_ptr<StreamCtx>> stream_ws;
@@ -643,8 +658,22 @@ int setup_device(Device& d) {
   // wide base tables for [e]B (7.3 MB), built once on the device
   STL_RC(d.wide.ensure(stl::kWideTableBytes));
   STL_TRY(stl::launch_wide_table(static_cast<uint4*>(d.wide.p), d.stream));
+  d.key_cache_log2 = g_key_cache_log2.load();
+  if (d.key_cache_log2 > 0) {
+    STL_RC(d.key_cache.ensure(stl::key_cache_bytes(d.key_cache_log2)));
+    STL_TRY(hipMemsetAsync(d.key_cache.p, 0, stl::key_cache_bytes(d.key_cache_log2), d.stream));
+  }
   STL_TRY(hipStreamSynchronize(d.stream));
   return STL_OK;
+}
+
+// The cache as a launch sees it, the knob read once per call: the sets in
+// use are the low 2^k of the allocated ones.
+void key_cache_exec(const Device& d, stl::VerifyExec& x) {
+  const int k = std::min(key_cache_in_use(), d.key_cache_log2);
+  if (k <= 0 || !d.key_cache.p) return;
+  x.key_cache = static_cast<uint4*>(d.key_cache.p);
+  x.key_cache_mask = (1u << k) - 1u;
 }
 
 void release_device(Device& d) {
@@ -656,8 +685,9 @@ void release_device(Device& d) {
   if (d.comm && g_rccl.ok) (void)g_rccl.CommDestroy(d.comm);
   d.comm = nullptr;
   for (DevBuf* b : {&d.sig, &d.msg, &d.pk, &d.bitmap, &d.pre, &d.off, &d.len, &d.ctr, &d.ctr2, &d.txid, &d.status,
-                    &d.wide, &d.gather, &d.counters})
+                    &d.wide, &d.gather, &d.counters, &d.key_cache})
     b->release();
+  d.key_cache_log2 = 0;
   {
     std::lock_guard<std::mutex> lk(d.ws_mu);
     for (auto& kv : d.stream_ws) {
@@ -843,6 +873,7 @@ int run_verify(Device& d, hipStream_t s, const uint8_t* sig, const uint8_t* msg_
   x.concurrent = concurrent;
   x.sub = chunk_for(d.grid, n);
   x.first = (uint32_t)g_tune_first_chunk.load();
+  key_cache_exec(d, x);
   uint32_t S = (uint32_t)std::max(1, std::min<int>(streams, (int)stl::kMaxVerifyStreams));
   if (x.clock || n <= x.sub || x.sub <= x.pair_max) S = 1;
   S = (uint32_t)std::min<size_t>(S, (n + x.sub - 1) / x.sub);
@@ -1465,6 +1496,11 @@ int stl_init(const stl_config* cfg) {
     const int ws = env_int("STL_MAX_STREAM_WORKSPACES", 0);
     if (ws >= 1 && ws <= 64) g_max_caller_streams.store(ws);
     if (c >= 15 && c <= 20) g_tune_sub_log2.store(c);
+    // sets of the decoded-key cache each device allocates: 2^10..2^24, 0 none
+    const int kc = env_int("STL_KEY_CACHE_LOG2", stl::kKeyCacheLog2Default);
+    g_key_cache_log2.store(kc == 0 || (kc >= stl::kKeyCacheLog2Min && kc <= stl::kKeyCacheLog2Max)
+                               ? kc
+                               : stl::kKeyCacheLog2Default);
   }
   int first = 0, want = -1, spd = 1;
   uint32_t cflags = 0;
@@ -1591,6 +1627,7 @@ int stl_debug_tuning(int key, int value) {
       case STL_TUNE_STREAM_WORKSPACES: return g_max_caller_streams.load();
       case STL_TUNE_RCCL_TIMEOUT_MS: return g_rccl_timeout_ms.load();
       case STL_TUNE_LONG_HASH: return g_tune_long_hash.load();
+      case STL_TUNE_KEY_CACHE: return key_cache_in_use();
       default: return STL_EINVAL;
     }
   }
@@ -1634,6 +1671,12 @@ int stl_debug_tuning(int key, int value) {
     case STL_TUNE_WIDE_MIN_ROWS:
       if (value < 0 || value > (int)stl::kPreChunk) return STL_EINVAL;
       return g_tune_wide_min.exchange(value);
+    case STL_TUNE_KEY_CACHE: {  // the previous value as a query reports it
+      if (value < 0 || value > g_key_cache_log2.load()) return STL_EINVAL;
+      const int prev = key_cache_in_use();
+      g_tune_key_cache.store(value);
+      return prev;
+    }
     default:
       return STL_EINVAL;
   }
@@ -1665,10 +1708,39 @@ int stl_debug_stream_contexts(void) {
   return di < 0 ? STL_ENODEV : caller_contexts(*g_devs[di]);
 }
 
+int stl_debug_key_cache_clear(void) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!g_init) return STL_ENODEV;
+  const int di = current_device_index();
+  if (di < 0) return STL_ENODEV;
+  Device& d = *g_devs[di];
+  if (!d.key_cache.p) return STL_OK;
+  STL_TRY(hipMemsetAsync(d.key_cache.p, 0, stl::key_cache_bytes(d.key_cache_log2), d.stream));
+  STL_TRY(hipStreamSynchronize(d.stream));
+  return STL_OK;
+}
+
+int stl_debug_key_cache_info(void** d_base, uint64_t* bytes, uint32_t* sets_log2, uint32_t* ways) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!g_init) return STL_ENODEV;
+  const int di = current_device_index();
+  if (di < 0) return STL_ENODEV;
+  const Device& d = *g_devs[di];
+  if (d_base) *d_base = d.key_cache.p;
+  if (bytes) *bytes = d.key_cache.p ? stl::key_cache_bytes(d.key_cache_log2) : 0;
+  if (sets_log2) *sets_log2 = (uint32_t)d.key_cache_log2;
+  if (ways) *ways = stl::kKeyCacheWays;
+  return STL_OK;
+}
+
 int stl_get_stats(stl_stats* out) {
-  if (!out || (out->struct_size != sizeof(stl_stats) && out->struct_size != offsetof(stl_stats, auto_dedup_chunks)))
+  // the struct as it grew: up to full_length_lanes .. phase_chunks, + auto_dedup_chunks, + the key-cache rows
+  if (!out || (out->struct_size != sizeof(stl_stats) && out->struct_size != offsetof(stl_stats, key_cache_hits) &&
+               out->struct_size != offsetof(stl_stats, auto_dedup_chunks)))
     return STL_EINVAL;
-  if (out->struct_size == sizeof(stl_stats)) out->auto_dedup_chunks = g_st_auto_dedup.load();
+  const bool has_cache = out->struct_size == sizeof(stl_stats);
+  if (out->struct_size >= offsetof(stl_stats, key_cache_hits)) out->auto_dedup_chunks = g_st_auto_dedup.load();
+  if (has_cache) out->key_cache_hits = out->key_cache_misses = 0;
   out->batches = g_st_batches.load();
   out->signatures = g_st_sigs.load();
   out->errors = g_st_errors.load();
@@ -1682,12 +1754,16 @@ int stl_get_stats(stl_stats* out) {
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto& d : g_devs) {  // device counters: waits for the work queued before the call
     if (!d->counters.p) continue;
-    unsigned long long c[2] = {0, 0};
+    unsigned long long c[4] = {0, 0, 0, 0};
     if (hipSetDevice(d->ordinal) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(c, d->counters.p, sizeof c, hipMemcpyDeviceToHost) != hipSuccess)
       return STL_EHIP;
     out->accepted += c[0];
     out->full_length_lanes += c[1];
+    if (has_cache) {
+      out->key_cache_hits += c[2];
+      out->key_cache_misses += c[3];
+    }
     d->timer.collect();
     std::lock_guard<std::mutex> tl(d->timer.mu);
     for (int i = 0; i < 4; ++i) out->phase_ns[i] += d->timer.ns[i];
@@ -1936,8 +2012,10 @@ int checksign_device(Device& d, hipStream_t s, bool blob, uint32_t kind, const u
   // batches; not blobs, whose signatures and keys come out of the pass): its
   // point role -- the two square-root chains, which need no message -- and
   // the key sample run on the other pool stream while the preimages hash.
+  stl::VerifyExec xc;  // the key cache, its knob read once for the call
+  key_cache_exec(d, xc);
   auto exec_for = [&](uint32_t cnt, uint32_t j) {
-    stl::VerifyExec x;
+    stl::VerifyExec x = xc;
     x.grid = verify_grid_for(d, cnt);
     x.ws_grid = d.grid;  // every workspace is verify_ws_bytes(d.grid, ...)
     x.pair_max = pair_max(d);

@@ -20,7 +20,10 @@ constexpr uint32_t kPreChunk = 1u << 20;
 // work counters of the main kernel's unit queue, one per chunk a launch_verify
 // call runs on a workspace (chunks >= 2^16 signatures, n < 2^32)
 constexpr uint32_t kMainQueueWords = 1u << 16;
-constexpr size_t kPreBytes = (size_t)kPreChunk * 224 + (size_t)kPreChunk / 8 + (size_t)kMainQueueWords * 4;
+// Decoded-key cache (stl_keycache.h): the rows of a chunk that missed it, one
+// index each, and one miss counter per chunk a launch runs on the workspace.
+constexpr size_t kMissBytes = (size_t)kPreChunk * 4 + (size_t)kMainQueueWords * 4;
+constexpr size_t kPreBytes = (size_t)kPreChunk * 224 + (size_t)kPreChunk / 8 + (size_t)kMainQueueWords * 4 + kMissBytes;
 // Per-batch key dedup (STL_DEDUP_KEYS), per kPreChunk signatures: an open-
 // addressing table of 2 * kPreChunk slots, representative / unique-id /
 // owner arrays, a counter, and the decoded keys (-A affine + ok, 5 x uint4).
@@ -34,10 +37,47 @@ constexpr uint32_t kWideKeys = 4096;
 constexpr uint32_t kWideKeyRepeat = 32;
 constexpr size_t kDedupBytes = kDedupSlots * 4 + 3 * (size_t)kPreChunk * 4 + 256 + (size_t)kPreChunk * 80 +
                                (size_t)kKeyTables * 81 * 16 + (size_t)kWideKeys * 137 * 9 * 16;
+// Byte offsets of the sub-buffers of a verify workspace for `grid` resident
+// workgroups: what the launch code addresses and verify_ws_bytes sizes.
+//   slots     per-lane tables, grid x kWsBytesPerBlock
+//   pre       HalfState x kPreChunk          fb        fallback words
+//   queue     the main kernel's unit-queue counters, one per chunk
+//   miss      rows that missed the key cache  miss_ctr  their count, one per chunk
+//   end       = verify_ws_bytes(grid): the key domain (kModeDedupKeys) follows
+//   kslots .. widetabs   hash slots, per-row representative, per-owner id and
+//             owner row, the distinct-key counter, the decoded keys, the
+//             shared and the wide key tables;  dedup_end = verify_ws_bytes(grid, true)
+struct VerifyWsLayout {
+  size_t slots, pre, fb, queue, miss, miss_ctr, end;
+  size_t kslots, rep, uid_of, owners, counter, keytab, keytabs, widetabs, dedup_end;
+};
+constexpr uint32_t kKeyTableQuads = 81;  // a key's 9-entry cached table (stl_verify_core.h kTableQuadsPerKey)
+inline VerifyWsLayout verify_ws_layout(uint32_t grid) {
+  VerifyWsLayout l;
+  l.slots = 0;
+  l.pre = kWsBytesPerBlock * grid;
+  l.fb = l.pre + (size_t)kPreChunk * 224;
+  l.queue = l.fb + (size_t)kPreChunk / 8;
+  l.miss = l.queue + (size_t)kMainQueueWords * 4;
+  l.miss_ctr = l.miss + (size_t)kPreChunk * 4;
+  l.end = l.miss_ctr + (size_t)kMainQueueWords * 4;
+  l.kslots = l.end;
+  l.rep = l.kslots + kDedupSlots * 4;
+  l.uid_of = l.rep + (size_t)kPreChunk * 4;
+  l.owners = l.uid_of + (size_t)kPreChunk * 4;
+  l.counter = l.owners + (size_t)kPreChunk * 4;
+  l.keytab = l.counter + 256;
+  l.keytabs = l.keytab + (size_t)kPreChunk * 80;
+  l.widetabs = l.keytabs + (size_t)kKeyTables * kKeyTableQuads * 16;
+  l.dedup_end = l.widetabs + (size_t)kWideKeys * 137 * 9 * 16;
+  return l;
+}
 // verify workspace for a grid of `grid` resident workgroups
 inline size_t verify_ws_bytes(uint32_t grid, bool dedup = false) {
-  return kWsBytesPerBlock * grid + kPreBytes + (dedup ? kDedupBytes : 0);
+  const VerifyWsLayout l = verify_ws_layout(grid);
+  return dedup ? l.dedup_end : l.end;
 }
+static_assert(kPreBytes % 16 == 0 && kDedupBytes % 16 == 0, "sub-buffers stay 16-byte aligned");
 
 // Kernel mode word: bit 0 = policy (STL_POLICY_*), bit 8 = full-length path
 // for every lane (STL_FULL_LENGTH), bit 9 = per-batch key dedup (STL_DEDUP_KEYS),
@@ -57,7 +97,8 @@ __host__ __device__ inline uint32_t core_policy(uint32_t mode) { return (mode & 
 
 const void* kernel_verify_msg32();
 // counters (nullable): device u64 [0] accept bits written, [1] lanes checked by
-// the full-length fallback path (stl_get_stats)
+// the full-length fallback path, [2] / [3] rows that hit / missed the decoded-
+// key cache (stl_get_stats)
 // pair_max: chunks of at most this many signatures (and 2x as many workspace
 // lanes in `grid`) run two lanes per signature (verify_main_pair_kernel);
 // the caller passes a quarter of the device's resident lanes, i.e. at most one
@@ -133,6 +174,11 @@ struct VerifyExec {
   // short verify_finish_keyed_kernel instead of the keyed point kernel
   const uint4* rdec = nullptr;
   hipEvent_t r_ready = nullptr;
+  // The device's decoded-key cache (stl_keycache.h) and the mask of the sets
+  // in use (STL_TUNE_KEY_CACHE, read once per call); nullptr: off.  Chunks
+  // that run the fused one-lane phase 1 look their keys up in it first.
+  uint4* key_cache = nullptr;
+  uint32_t key_cache_mask = 0;
 };
 // The pre-checks and R's decoding of rows [0, n) into rdec (5 quads per row),
 // for VerifyExec::rdec.

@@ -22,6 +22,7 @@
 // resident lanes.
 #include "stl_base_table.h"
 #include "stl_kernels.h"
+#include "stl_keycache.h"
 #include "stl_sign.h"
 #include "stl_txblob.h"
 #include "stl_verify_core.h"
@@ -205,7 +206,11 @@ __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_point_k
 // and the chunk pays one kernel boundary instead of two -- the scalar
 // kernel alone ends in a ragged last round (3.2 rounds of 5 workgroups per
 // CU for 2^20 signatures).
-template <bool PRE_K>
+// A_READY: the key-cache kernels below ran first and left -A's x (words 20-28
+// of the row's state) and its decoding's verdict (word 29): the lane takes y
+// from the key bytes and decodes only R.
+constexpr int kKeyReadyQuad = 5;  // quads 5-7 = words 20-31 of the HalfState
+template <bool PRE_K, bool A_READY>
 __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_prep_kernel(
     const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg_or_k, const uint8_t* __restrict__ pk,
     uint32_t base, uint32_t cnt, uint32_t policy, uint4* __restrict__ pre, uint64_t* __restrict__ fb_words) {
@@ -233,7 +238,21 @@ __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_prep_ke
         st_state(q + i, make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]));
     }
   }
-  verify_phase1_points(h, R, S, A, core_policy(policy));
+  if (A_READY) {
+    uint32_t kw[12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const uint4 v = ld_state(q + kKeyReadyQuad + i);
+      kw[4 * i] = v.x; kw[4 * i + 1] = v.y; kw[4 * i + 2] = v.z; kw[4 * i + 3] = v.w;
+    }
+    fe nAx, nAy;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) nAx.v[i] = kw[i];
+    fe_frombytes(nAy, A);
+    verify_phase1_points_keyed(h, R, S, A, core_policy(policy), nAx, nAy, kw[9] != 0);
+  } else {
+    verify_phase1_points(h, R, S, A, core_policy(policy));
+  }
   if ((policy & kModeFullLength) && (h.tops & kHalfOk)) h.tops |= kHalfFallback;
   if (live) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&h);
@@ -378,16 +397,6 @@ __global__ __launch_bounds__(kBlock) void verify_finish_pair_kernel(uint32_t cnt
 //   verify_point_kernel_keyed  the point half with only R decoded.
 constexpr uint32_t kKeyEmpty = 0xffffffffu;
 constexpr int kKeyProbes = 32;
-
-__device__ __forceinline__ uint32_t key_hash(const uint32_t A[8]) {
-  uint32_t h = A[0] * 0x9E3779B1u;
-  h ^= A[1] * 0x85EBCA6Bu;
-  h = (h << 13) | (h >> 19);
-  h ^= A[2] * 0xC2B2AE35u;
-  h ^= A[5] * 0x27D4EB2Fu;
-  h ^= h >> 16;
-  return h * 0x7FEB352Du;
-}
 
 // Key-repeat sample of the device-resident API's automatic dedup choice
 // (stl_api.cpp, StreamCtx::auto_flag): one workgroup puts up to kSampleKeys
@@ -553,6 +562,139 @@ __global__ __launch_bounds__(kBlock, 4) void key_decode_kernel(const uint8_t* __
     affine_to_p3(P, negA.X, negA.Y);
     build_cached_table(TableView::contiguous(keytabs + (size_t)u * kTableQuadsPerKey), P);
   }
+}
+
+// ---- decoded-key cache (stl_keycache.h) ----
+// Ahead of verify_prep_kernel<.., true>, for chunks that run one lane per
+// signature without key dedup:
+//   key_cache_lookup_kernel  one lane per row: gathers the tags of the key's
+//                            set, and a way with the key's tag offers its x; a
+//                            certified x goes into the row's state, any other
+//                            row onto the chunk's miss list;
+//   key_cache_fill_kernel    one lane per missed row, compacted: the full
+//                            decoding, its x and verdict into the row's state,
+//                            and a decodable key with x != 0 into the cache.
+// Both write words 20-31 of the row's HalfState: x(-A) as 9 canonical limbs
+// (the same limbs on a hit and on a miss), word 29 = the decoding is ok.
+__device__ __forceinline__ void st_key_ready(uint4* __restrict__ pre, uint32_t t, const fe& X, bool ok) {
+  uint4* q = pre + (size_t)t * 14 + kKeyReadyQuad;
+  st_state(q, make_uint4(X.v[0], X.v[1], X.v[2], X.v[3]));
+  st_state(q + 1, make_uint4(X.v[4], X.v[5], X.v[6], X.v[7]));
+  st_state(q + 2, make_uint4(X.v[8], ok ? 1u : 0u, 0u, 0u));
+}
+
+// The set's tags (words 0-11 of the set: three quads) against the key's tag:
+// bit w = way w holds it.
+__device__ __forceinline__ uint32_t tag_matches(const uint4 t[3], const uint32_t tag[2]) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    m |= (t[i].x == tag[0] && t[i].y == tag[1]) ? 1u << (2 * i) : 0u;
+    m |= (t[i].z == tag[0] && t[i].w == tag[1]) ? 2u << (2 * i) : 0u;
+  }
+  return m;
+}
+static_assert(kKeyCacheWays == 6 && kKeyCacheTagWord == 0 && kKeyCacheXWord == 16, "tag_matches and the kernels below");
+
+__global__ __launch_bounds__(kBlock) void key_cache_lookup_kernel(const uint8_t* __restrict__ pk, uint32_t base,
+                                                                  uint32_t cnt, const uint4* cache, uint32_t mask,
+                                                                  uint4* __restrict__ pre, uint32_t* __restrict__ miss,
+                                                                  uint32_t* __restrict__ miss_ctr) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool live = t < cnt;
+  uint32_t A[8];
+  ld8(A, pk + 32 * ((size_t)base + (live ? t : cnt - 1)));
+  const uint4* set = cache + (size_t)key_cache_set(key_hash(A), mask) * (kKeyCacheSetBytes / 16);
+  uint32_t tag[2];
+  key_cache_tag(tag, A);
+  const uint4 tq[3] = {set[0], set[1], set[2]};
+  const uint32_t match = tag_matches(tq, tag);
+  const int way = match ? __ffs((int)match) - 1 : -1;  // the lowest way with the key's tag
+  bool hit = false;
+  fe X;
+  if (__ballot(way >= 0) != 0) {  // a cold wave skips the check
+    uint32_t xb[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (way >= 0) {
+      const uint4 a = set[kKeyCacheXWord / 4 + 2 * way], b = set[kKeyCacheXWord / 4 + 2 * way + 1];
+      xb[0] = a.x; xb[1] = a.y; xb[2] = a.z; xb[3] = a.w;
+      xb[4] = b.x; xb[5] = b.y; xb[6] = b.z; xb[7] = b.w;
+    }
+    hit = key_cache_certify(X, A, xb) && way >= 0 && live;
+  }
+  if (hit) st_key_ready(pre, t, X, true);
+  // the miss list: one atomic per wave
+  const bool missed = live && !hit;
+  const uint64_t m = __ballot(missed);
+  if (m == 0) return;
+  const int leader = __ffsll((unsigned long long)m) - 1;
+  uint32_t b0 = 0;
+  if ((int)lane == leader) b0 = atomicAdd(miss_ctr, (uint32_t)__popcll(m));
+  b0 = __shfl(b0, leader);
+  if (missed) miss[b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;
+}
+
+// One missed row t of the chunk: decoded, into its state and (if cacheable) the cache.
+__device__ __forceinline__ void key_cache_fill_row(const uint8_t* __restrict__ pk, uint32_t base, uint4* cache,
+                                                   uint32_t mask, uint4* __restrict__ pre, uint32_t t) {
+  uint32_t A[8];
+  ld8(A, pk + 32 * ((size_t)base + t));
+  ge_p3 negA;
+  const bool ok = ge_frombytes_negate_vartime(negA, A);
+  uint32_t xb[8];
+  fe_tobytes(xb, negA.X);
+  fe X;
+  fe_frombytes(X, xb);
+  st_key_ready(pre, t, X, ok);
+  uint32_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) nz |= xb[k];
+  if (!ok || nz == 0) return;  // never cached: such a key takes the chain every time
+  const uint32_t h = key_hash(A);
+  uint4* set = cache + (size_t)key_cache_set(h, mask) * (kKeyCacheSetBytes / 16);
+  uint32_t tag[2];
+  key_cache_tag(tag, A);
+  const uint4 tq[3] = {set[0], set[1], set[2]};
+  const uint32_t match = tag_matches(tq, tag);
+  const uint32_t tw[12] = {tq[0].x, tq[0].y, tq[0].z, tq[0].w, tq[1].x, tq[1].y,
+                           tq[1].z, tq[1].w, tq[2].x, tq[2].y, tq[2].z, tq[2].w};
+  bool same[kKeyCacheWays], empty[kKeyCacheWays];
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyCacheWays; ++w) {
+    const uint4 c = set[kKeyCacheXWord / 4 + 2 * w], d = set[kKeyCacheXWord / 4 + 2 * w + 1];
+    same[w] = ((match >> w) & 1u) != 0;
+    empty[w] = (tw[2 * w] | tw[2 * w + 1] | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w) == 0u;
+  }
+  const uint32_t v = key_cache_victim(h, same, empty);
+  // plain stores: a reader that sees part of them fails its check and misses
+  uint32_t* sw = reinterpret_cast<uint32_t*>(set);
+  *reinterpret_cast<uint2*>(sw + kKeyCacheTagWord + 2 * v) = make_uint2(tag[0], tag[1]);
+  uint4* xs = set + kKeyCacheXWord / 4 + 2 * v;
+  xs[0] = make_uint4(xb[0], xb[1], xb[2], xb[3]);
+  xs[1] = make_uint4(xb[4], xb[5], xb[6], xb[7]);
+}
+
+// The grid covers cnt rows (the host cannot know the miss count); lanes past
+// the count exit.  A grid capped at the resident workgroups, striding over the
+// list, measured slower cold (0.89 vs 0.82 ms per 2^20 misses) and the same
+// warm: the 0.09 ms a warm 2^20-row chunk spends here is one wave's latency
+// through the chain for its last hundred misses, not the empty workgroups.
+// Lane 0 adds the chunk's hits and misses to the device's statistics
+// (counters[2], [3]).
+__global__ __launch_bounds__(kBlock, 4) void key_cache_fill_kernel(const uint8_t* __restrict__ pk, uint32_t base,
+                                                                   uint32_t cnt, uint4* cache, uint32_t mask,
+                                                                   uint4* __restrict__ pre,
+                                                                   const uint32_t* __restrict__ miss,
+                                                                   const uint32_t* __restrict__ miss_ctr,
+                                                                   unsigned long long* __restrict__ counters) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t nm = *miss_ctr;  // <= cnt
+  if (i == 0 && counters) {
+    atomicAdd(&counters[2], (unsigned long long)(cnt - nm));
+    atomicAdd(&counters[3], (unsigned long long)nm);
+  }
+  if (i >= nm) return;  // no wave-level collective in this kernel
+  key_cache_fill_row(pk, base, cache, mask, pre, miss[i]);
 }
 
 // The chunk's wide key tables j*(-A), j = 0..136, in two stages
@@ -1992,7 +2134,7 @@ bool verify_pair_points(uint32_t n, uint32_t policy, const VerifyExec& x) {
 hipError_t launch_verify_points(const uint8_t* sig, const uint8_t* pk, uint32_t n, uint32_t policy,
                                 const VerifyExec& x, hipStream_t stream) {
   if (!verify_pair_points(n, policy, x)) return hipErrorInvalidValue;
-  uint4* pre = x.ws[0] + (size_t)x.grid * (kWsBytesPerBlock / 16);
+  uint4* pre = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(x.ws[0]) + verify_ws_layout(x.grid).pre);
   const dim3 gp((2 * n + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(verify_prep_pair_kernel<false>, gp, dim3(kBlock), 0, stream, sig, nullptr, pk, 0u, n, policy,
                      pre, 0u);
@@ -2008,17 +2150,19 @@ struct KeyDomain {
 };
 static KeyDomain key_domain(uint4* ws, uint32_t grid) {
   KeyDomain k;
-  uint32_t* dd = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ws) + verify_ws_bytes(grid));
-  k.kslots = dd;
-  k.rep = k.kslots + kDedupSlots;
-  k.uid_of = k.rep + kPreChunk;
-  k.owners = k.uid_of + kPreChunk;
-  k.counter = k.owners + kPreChunk;
-  k.keytab = reinterpret_cast<uint4*>(k.counter + 64);
-  k.keytabs = k.keytab + (size_t)kPreChunk * 5;
-  k.widetabs = k.keytabs + (size_t)kKeyTables * kTableQuadsPerKey;
+  const VerifyWsLayout l = verify_ws_layout(grid);
+  uint8_t* b = reinterpret_cast<uint8_t*>(ws);
+  k.kslots = reinterpret_cast<uint32_t*>(b + l.kslots);
+  k.rep = reinterpret_cast<uint32_t*>(b + l.rep);
+  k.uid_of = reinterpret_cast<uint32_t*>(b + l.uid_of);
+  k.owners = reinterpret_cast<uint32_t*>(b + l.owners);
+  k.counter = reinterpret_cast<uint32_t*>(b + l.counter);
+  k.keytab = reinterpret_cast<uint4*>(b + l.keytab);
+  k.keytabs = reinterpret_cast<uint4*>(b + l.keytabs);
+  k.widetabs = reinterpret_cast<uint4*>(b + l.widetabs);
   return k;
 }
+static_assert(kKeyTableQuads == kTableQuadsPerKey, "verify_ws_layout's key tables");
 
 // The dedup chain over rows [base, base+cnt) (cnt <= kPreChunk): hash slots,
 // owners, decoded keys, shared or wide key tables -- rep[i] for row base+i.
@@ -2057,21 +2201,24 @@ hipError_t launch_key_domain_ws(const uint8_t* pk, uint32_t n, uint4* ws, uint32
 
 // One chunk (<= kPreChunk signatures at [base, base+cnt)) on one stream and
 // workspace: phase 1, main, fallback.  `qctr` is the chunk's zeroed counter
-// of the main kernel's unit queue.
+// of the main kernel's unit queue, `mctr` its zeroed key-cache miss counter
+// (nullptr: no cache).
 static hipError_t verify_chunk(const uint8_t* sig, const uint8_t* msg_or_k, const uint8_t* pk, uint32_t base,
                                uint32_t cnt, uint64_t* bitmap, uint32_t policy, bool pre_k, const VerifyExec& x,
-                               hipStream_t stream, uint4* ws, uint32_t* qctr, const PhaseClock* clock) {
+                               hipStream_t stream, uint4* ws, uint32_t* qctr, uint32_t* mctr,
+                               const PhaseClock* clock) {
   const uint32_t grid = x.grid, pair_max = x.pair_max;
   const uint4* wide = x.wide;
   unsigned long long* counters = x.counters;
   auto mark = [&](int i) {
     if (clock) clock->mark(clock->ctx, stream, i);
   };
-  // ws = [per-lane slots: grid x kWsBytesPerBlock][HalfState x kPreChunk][fallback words][queue counters]
-  //      [dedup (kModeDedupKeys): slots, rep, uid_of, owners, counter, decoded keys]
+  // the workspace's sub-buffers: verify_ws_layout (stl_kernels.h)
+  const VerifyWsLayout lay = verify_ws_layout(grid);
   uint4* slots = ws;
-  uint4* pre = ws + (size_t)grid * (kWsBytesPerBlock / 16);
-  uint64_t* fb = reinterpret_cast<uint64_t*>(pre + (size_t)kPreChunk * 14);
+  uint4* pre = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(ws) + lay.pre);
+  uint64_t* fb = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(ws) + lay.fb);
+  uint32_t* miss = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ws) + lay.miss);
   const bool dedup = (policy & kModeDedupKeys) != 0;
   // a launch-wide key domain (KeyDomain: one key table for every chunk of
   // the launch, in x.key_ws) or this chunk's own, in its workspace
@@ -2112,12 +2259,25 @@ static hipError_t verify_chunk(const uint8_t* sig, const uint8_t* msg_or_k, cons
       else
         hipLaunchKernelGGL(verify_prep_pair_kernel<false>, dim3(nblk), dim3(kBlock), 0, stream, sig, msg_or_k,
                            pk, base, cnt, policy, pre, nbs);
+    } else if (fused && x.key_cache && mctr) {
+      // the keys' x from the device's cache where it certifies, decoded (and
+      // cached) where not; then phase 1 with only R's square root
+      hipLaunchKernelGGL(key_cache_lookup_kernel, g1, dim3(kBlock), 0, stream, pk, base, cnt, x.key_cache,
+                         x.key_cache_mask, pre, miss, mctr);
+      hipLaunchKernelGGL(key_cache_fill_kernel, g1, dim3(kBlock), 0, stream, pk, base, cnt, x.key_cache,
+                         x.key_cache_mask, pre, miss, mctr, counters);
+      if (pre_k)
+        hipLaunchKernelGGL((verify_prep_kernel<true, true>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
+                           policy, pre, fb);
+      else
+        hipLaunchKernelGGL((verify_prep_kernel<false, true>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
+                           policy, pre, fb);
     } else if (fused && pre_k)
-      hipLaunchKernelGGL(verify_prep_kernel<true>, g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt, policy,
-                         pre, fb);
+      hipLaunchKernelGGL((verify_prep_kernel<true, false>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
+                         policy, pre, fb);
     else if (fused)
-      hipLaunchKernelGGL(verify_prep_kernel<false>, g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt, policy,
-                         pre, fb);
+      hipLaunchKernelGGL((verify_prep_kernel<false, false>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
+                         policy, pre, fb);
     else if (pre_k)
       hipLaunchKernelGGL(verify_scalar_kernel<true>, g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt, pre);
     else
@@ -2190,8 +2350,11 @@ static hipError_t verify_chunk(const uint8_t* sig, const uint8_t* msg_or_k, cons
 
 // queue counters of workspace ws (after the fallback words)
 static uint32_t* queue_counters(uint4* ws, uint32_t grid) {
-  uint4* pre = ws + (size_t)grid * (kWsBytesPerBlock / 16);
-  return reinterpret_cast<uint32_t*>(reinterpret_cast<uint64_t*>(pre + (size_t)kPreChunk * 14) + kPreChunk / 64);
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ws) + verify_ws_layout(grid).queue);
+}
+// key-cache miss counters of workspace ws, one per chunk like the queue counters
+static uint32_t* miss_counters(uint4* ws, uint32_t grid) {
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ws) + verify_ws_layout(grid).miss_ctr);
 }
 
 hipError_t launch_verify(const uint8_t* sig, const uint8_t* msg_or_k, const uint8_t* pk, uint32_t n,
@@ -2227,6 +2390,16 @@ hipError_t launch_verify(const uint8_t* sig, const uint8_t* msg_or_k, const uint
       if (e != hipSuccess) return e;
     }
   }
+  // ... and its key-cache miss counters, where chunks can take the cached path
+  const bool cached = x.key_cache != nullptr && x.fused_prep != 0 && (policy & kModeDedupKeys) == 0 &&
+                      !(nchunks == 1 && pair_point_chunk(n, policy, x));
+  if (cached) {
+    for (uint32_t j = 0; j < S; ++j) {
+      const uint64_t cj = (nchunks - j + S - 1) / S;
+      e = hipMemsetAsync(miss_counters(x.ws[j], x.grid), 0, cj * 4, x.streams[j]);
+      if (e != hipSuccess) return e;
+    }
+  }
   // one key domain for every chunk of the launch (see VerifyExec::key_ready):
   // built by chunk 0 on streams[0] right after its scalar kernel
   VerifyExec xk = x;
@@ -2253,7 +2426,8 @@ hipError_t launch_verify(const uint8_t* sig, const uint8_t* msg_or_k, const uint
     const uint32_t cnt = n - base < cap ? n - base : cap;
     uint32_t* q = x.main_queue ? queue_counters(x.ws[j], x.grid) + c / S : nullptr;
     if (shared_keys) xk.key_build = c == 0 && !x.key_stream;
-    e = verify_chunk(sig, msg_or_k, pk, base, cnt, bitmap, policy, pre_k, xk, x.streams[j], x.ws[j], q,
+    uint32_t* mq = cached ? miss_counters(x.ws[j], x.grid) + c / S : nullptr;
+    e = verify_chunk(sig, msg_or_k, pk, base, cnt, bitmap, policy, pre_k, xk, x.streams[j], x.ws[j], q, mq,
                      S > 1 ? nullptr : x.clock);
     if (e != hipSuccess) return e;
   }

@@ -756,7 +756,8 @@ class Stats(ctypes.Structure):
                 ("host_ns", ctypes.c_uint64), ("gather_ns", ctypes.c_uint64),
                 ("accepted", ctypes.c_uint64), ("full_length_lanes", ctypes.c_uint64),
                 ("phase_ns", ctypes.c_uint64 * 4), ("phase_chunks", ctypes.c_uint64),
-                ("auto_dedup_chunks", ctypes.c_uint64)]
+                ("auto_dedup_chunks", ctypes.c_uint64),
+                ("key_cache_hits", ctypes.c_uint64), ("key_cache_misses", ctypes.c_uint64)]
 
 
 # stl_stats.phase_ns: [0] the first phase-1 kernel -- all of phase 1 when it
@@ -818,6 +819,7 @@ TUNE_SHARED_KEYS = N.STL_TUNE_SHARED_KEYS
 TUNE_WIDE_MIN_ROWS = N.STL_TUNE_WIDE_MIN_ROWS
 TUNE_R_AHEAD = N.STL_TUNE_R_AHEAD
 TUNE_FIRST_CHUNK = N.STL_TUNE_FIRST_CHUNK
+TUNE_KEY_CACHE = N.STL_TUNE_KEY_CACHE
 
 
 def debug_tuning(key, value):
@@ -893,7 +895,22 @@ def execution_settings():
         ("fused_prep", TUNE_FUSED_PREP), ("main_queue", TUNE_MAIN_QUEUE), ("streams", TUNE_STREAMS),
         ("chunk_log2", TUNE_CHUNK_LOG2), ("quad", TUNE_QUAD), ("long_hash", TUNE_LONG_HASH),
         ("shared_keys", TUNE_SHARED_KEYS), ("wide_min_rows", TUNE_WIDE_MIN_ROWS),
-        ("r_ahead", TUNE_R_AHEAD), ("first_chunk", TUNE_FIRST_CHUNK))}
+        ("r_ahead", TUNE_R_AHEAD), ("first_chunk", TUNE_FIRST_CHUNK), ("key_cache", TUNE_KEY_CACHE))}
+
+
+def key_cache_clear():
+    """stl_debug_key_cache_clear: empty the current device's decoded-key cache."""
+    N.check(N.load().stl_debug_key_cache_clear(), "stl_debug_key_cache_clear")
+
+
+def key_cache_info():
+    """stl_debug_key_cache_info: {"ptr", "bytes", "sets_log2", "ways"} of the
+    current device's decoded-key cache (bytes 0: none)."""
+    p, b = ctypes.c_void_p(), ctypes.c_uint64()
+    k, w = ctypes.c_uint32(), ctypes.c_uint32()
+    N.check(N.load().stl_debug_key_cache_info(ctypes.byref(p), ctypes.byref(b), ctypes.byref(k), ctypes.byref(w)),
+            "stl_debug_key_cache_info")
+    return {"ptr": p.value or 0, "bytes": b.value, "sets_log2": k.value, "ways": w.value}
 
 
 def sign_batch_device(seed, msg, stream=None):
