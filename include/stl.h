@@ -276,6 +276,38 @@ int stl_signed_blob_verify_batch_device(uint32_t kind, const uint8_t *d_blobs, c
                                         const uint32_t *d_len, size_t n, uint64_t *d_bitmap_words, uint8_t *d_status,
                                         uint8_t *d_id, uint32_t flags, void *stream);
 
+/* ---- signer authority: account IDs and the master-key match ----
+ * After checkSign, Transactor::checkSig (Transactor.cpp:151-170) asks whether
+ * the signing key is the key authorised for the account: first
+ * mSigningPubKey.getAccountID() == mTxnAccountID (the master key), else the
+ * account's RegularKey from ledger state.  getAccountID() of an account public
+ * key is Hash160(key) = RIPEMD160(SHA256(key)) (RippleAddress.cpp:361-363,
+ * HashUtilities.cpp:22-29).  These calls compute the IDs and the first
+ * comparison for a whole batch; the RegularKey comparison stays with the
+ * caller.  Single device; the host forms upload, run the device form and copy
+ * back.  A failure is a negative code, never a verdict. */
+#define STL_ACCOUNT_ID_BYTES 20u
+/* Hash160 of n 32-byte account public keys = RippleAddress::getAccountID
+ * (RippleAddress.cpp:361-363).  account_id: n*20 bytes, the digest bytes in
+ * OpenSSL's order.  Device form: d_pk 16-byte aligned, d_account_id 4-byte
+ * aligned (else STL_EINVAL); exactly n*20 bytes are written. */
+int stl_account_id_batch(const uint8_t *pk, size_t n, uint8_t *account_id); /* host memory, synchronous */
+int stl_account_id_batch_device(const uint8_t *d_pk, size_t n, uint8_t *d_account_id, void *stream);
+
+#define STL_SIGNER_NOT_MASTER 0u /* Hash160(SigningPubKey) != Account: the caller checks RegularKey (ledger state) */
+#define STL_SIGNER_MASTER 1u     /* == Account: Transactor::checkSig's first branch */
+#define STL_SIGNER_UNDECIDED 2u  /* row is not STL_TX_OK, or Account is not 20 bytes: the caller's own path */
+/* Serialized transactions as stl_tx_blob_verify_batch takes them.  d_signer_id: n*20; d_account: n*20 or NULL;
+ * d_authority: n bytes.  Independent of the verify: says who signed, not whether the signature is good.
+ * A row's status is the one stl_tx_blob_prepare_device reports.  STL_TX_OK row: signer_id =
+ * Hash160(SigningPubKey); account = the Account field's bytes when it has 20 (else zero, and the row is
+ * UNDECIDED).  Any other row: zero IDs, UNDECIDED.  d_signer_id and d_account 4-byte aligned (else
+ * STL_EINVAL).  account is also the source account of CanonicalTXSet's apply order (CanonicalTXSet.cpp:75-81). */
+int stl_tx_blob_signer_batch_device(const uint8_t *d_blobs, const uint64_t *d_offset, const uint32_t *d_len, size_t n,
+                                    uint8_t *d_signer_id, uint8_t *d_account, uint8_t *d_authority, void *stream);
+int stl_tx_blob_signer_batch(const uint8_t *blobs, const uint64_t *offset, const uint32_t *len, size_t n,
+                             uint8_t *signer_id, uint8_t *account, uint8_t *authority);
+
 /* ---- multi-GPU: one process per GPU ----
  * Verification shards by index with no exchange; the accept bitmaps are
  * gathered with RCCL over xGMI.  rank r owns signatures

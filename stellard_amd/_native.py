@@ -61,6 +61,12 @@ STL_TX_OK = 0
 STL_TX_DEFERRED = 1
 STL_TX_MALFORMED = 2
 
+# signer authority (stl_account_id_batch*, stl_tx_blob_signer_batch*)
+STL_ACCOUNT_ID_BYTES = 20
+STL_SIGNER_NOT_MASTER = 0
+STL_SIGNER_MASTER = 1
+STL_SIGNER_UNDECIDED = 2
+
 # Every entry point include/stl.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U8P = ctypes.c_void_p
@@ -135,6 +141,10 @@ SYMBOLS = [
     ("stl_keyset_verify_by_key", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, ctypes.c_uint32]),
     ("stl_keyset_signed_blob_verify_batch_device", ctypes.c_int,
      [_P, ctypes.c_uint32, _U8P, _P, _P, ctypes.c_size_t, _P, _U8P, _U8P, ctypes.c_uint32, _P, _P]),
+    ("stl_account_id_batch", ctypes.c_int, [_U8P, ctypes.c_size_t, _U8P]),
+    ("stl_account_id_batch_device", ctypes.c_int, [_U8P, ctypes.c_size_t, _U8P, _P]),
+    ("stl_tx_blob_signer_batch_device", ctypes.c_int, [_U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),
+    ("stl_tx_blob_signer_batch", ctypes.c_int, [_U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -42,6 +42,7 @@
 #include "stl_keycache.h"
 #include "stl_keyset.h"
 #include "stl_keyset_map.h"
+#include "stl_signer.h"
 
 namespace {
 
@@ -2942,6 +2943,108 @@ int stl_debug_keyset_rows(const stl_keyset* ks, uint32_t key, uint32_t first_row
   STL_TRY(hipDeviceSynchronize());
   STL_TRY(hipMemcpy(out_words, src, (size_t)nrows * g.row_bytes, hipMemcpyDeviceToHost));
   return STL_OK;
+}
+
+// ---- signer authority: account IDs and the master-key match (stl_signer.hip) ----
+
+int stl_account_id_batch_device(const uint8_t* d_pk, size_t n, uint8_t* d_account_id, void* stream) {
+  if (n == 0) return STL_OK;
+  if (!d_pk || !d_account_id || n > 0xffffffc0ull) return STL_EINVAL;
+  // the kernel's 16-byte loads and dword stores: refused, never attempted
+  if (((uintptr_t)d_pk & 15u) != 0 || ((uintptr_t)d_account_id & 3u) != 0) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  STL_TRY(stl::launch_account_id(d_pk, (uint32_t)n, d_account_id, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_tx_blob_signer_batch_device(const uint8_t* d_blobs, const uint64_t* d_offset, const uint32_t* d_len, size_t n,
+                                    uint8_t* d_signer_id, uint8_t* d_account, uint8_t* d_authority, void* stream) {
+  if (n == 0) return STL_OK;
+  if (!d_blobs || !d_offset || !d_len || !d_signer_id || !d_authority || n > 0xffffffc0ull) return STL_EINVAL;
+  if (((uintptr_t)d_signer_id & 3u) != 0 || ((uintptr_t)d_account & 3u) != 0) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  STL_TRY(stl::launch_tx_signer(d_blobs, d_offset, d_len, (uint32_t)n, d_signer_id, d_account, d_authority,
+                                static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_account_id_batch(const uint8_t* pk, size_t n, uint8_t* account_id) {
+  if (n == 0) return STL_OK;
+  if (!pk || !account_id || n > 0xffffffc0ull) return STL_EINVAL;
+  STL_RC(ensure_init());
+  if (g_devs.empty()) return STL_ENODEV;
+  CallSpan span{"stl_account_id_batch", n};
+  DeviceGuard guard;
+  Device& d = *g_devs[0];
+  std::lock_guard<std::mutex> dl(d.mu);
+  std::vector<uint8_t> host(n * STL_ACCOUNT_ID_BYTES);
+  auto go = [&]() -> int {
+    STL_TRY(hipSetDevice(d.ordinal));
+    STL_RC(d.pk.ensure(n * 32));
+    STL_RC(d.msg.ensure(n * STL_ACCOUNT_ID_BYTES));
+    STL_TRY(hipMemcpyAsync(d.pk.p, pk, n * 32, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(stl::launch_account_id(static_cast<const uint8_t*>(d.pk.p), (uint32_t)n, static_cast<uint8_t*>(d.msg.p),
+                                   d.stream));
+    STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, host.size(), hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {  // nothing may still read the caller's rows or write host
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  std::memcpy(account_id, host.data(), host.size());
+  return span.finish(STL_OK);
+}
+
+int stl_tx_blob_signer_batch(const uint8_t* blobs, const uint64_t* offset, const uint32_t* len, size_t n,
+                             uint8_t* signer_id, uint8_t* account, uint8_t* authority) {
+  if (n == 0) return STL_OK;
+  if (!blobs || !offset || !len || !signer_id || !authority || n > 0xffffffc0ull) return STL_EINVAL;
+  STL_RC(ensure_init());
+  if (g_devs.empty()) return STL_ENODEV;
+  CallSpan span{"stl_tx_blob_signer_batch", n};
+  DeviceGuard guard;
+  Device& d = *g_devs[0];
+  std::lock_guard<std::mutex> dl(d.mu);
+  std::vector<uint64_t> roff, row_end;
+  uint64_t base = 0, bytes = 0;
+  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
+  const size_t idb = n * STL_ACCOUNT_ID_BYTES;
+  std::vector<uint8_t> host(2 * idb + n);  // signer IDs, accounts, authority
+  auto go = [&]() -> int {
+    STL_TRY(hipSetDevice(d.ordinal));
+    STL_RC(d.pre.ensure(bytes + 16));
+    STL_RC(d.off.ensure(n * 8));
+    STL_RC(d.len.ensure(n * 4));
+    STL_RC(d.msg.ensure(idb));
+    STL_RC(d.txid.ensure(idb));
+    STL_RC(d.status.ensure(n));
+    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(stl::launch_tx_signer(static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
+                                  static_cast<const uint32_t*>(d.len.p), (uint32_t)n, static_cast<uint8_t*>(d.msg.p),
+                                  account ? static_cast<uint8_t*>(d.txid.p) : nullptr,
+                                  static_cast<uint8_t*>(d.status.p), d.stream));
+    STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, idb, hipMemcpyDeviceToHost, d.stream));
+    if (account) STL_TRY(hipMemcpyAsync(host.data() + idb, d.txid.p, idb, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipMemcpyAsync(host.data() + 2 * idb, d.status.p, n, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {  // nothing may still read the caller's rows or write host
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  std::memcpy(signer_id, host.data(), idb);
+  if (account) std::memcpy(account, host.data() + idb, idb);
+  std::memcpy(authority, host.data() + 2 * idb, n);
+  return span.finish(STL_OK);
 }
 
 }  // extern "C"

@@ -69,6 +69,7 @@ constexpr uint32_t kTxMalformed = 2;  // canonical, but SigningPubKey != 32 B or
 constexpr uint32_t kCodeSigningPubKey = 0x70003u;  // VL 3
 constexpr uint32_t kCodeTxnSignature = 0x70004u;   // VL 4
 constexpr uint32_t kCodeSignature = 0x70006u;      // VL 6
+constexpr uint32_t kCodeAccount = 0x80001u;        // ACCOUNT 1
 constexpr uint32_t kCodeTxnSignatures = 0xF0003u;  // ARRAY 3
 constexpr uint32_t kCodeObjectEnd = 0xE0001u;      // STI_OBJECT, 1
 constexpr uint32_t kCodeArrayEnd = 0xF0001u;       // STI_ARRAY, 1
@@ -252,6 +253,7 @@ struct TxLayout {
   uint32_t pk_off, pk_len;    // SigningPubKey payload (pk_len 0xffffffff: absent)
   uint32_t sig_off, sig_len;  // signature payload (TxnSignature; Signature for validations)
   uint32_t xs0, xe0, xs1, xe1, xs2, xe2;
+  uint32_t acct_off, acct_len;  // top-level Account payload (acct_len 0xffffffff: absent); stl_signer.hip
 };
 
 template <typename Bytes>
@@ -268,8 +270,8 @@ template <typename Bytes>
 STL_HD void tx_blob_parse(const Bytes& b, uint32_t len, TxLayout& t, uint32_t sig_code = kCodeTxnSignature,
                           uint32_t min_len = kTxMinBytes, uint32_t format = kFormatTx) {
   t.status = kTxDeferred;
-  t.pk_off = t.sig_off = 0;
-  t.pk_len = t.sig_len = 0xffffffffu;
+  t.pk_off = t.sig_off = t.acct_off = 0;
+  t.pk_len = t.sig_len = t.acct_len = 0xffffffffu;
   t.xs0 = t.xe0 = t.xs1 = t.xe1 = t.xs2 = t.xe2 = len;
   if (len < min_len || len > kTxMaxBytes) return;
   uint32_t last[kBlobMaxDepth + 1];
@@ -370,6 +372,9 @@ STL_HD void tx_blob_parse(const Bytes& b, uint32_t len, TxLayout& t, uint32_t si
       } else if (depth == 0 && code == sig_code) {
         t.sig_off = pos;
         t.sig_len = size;
+      } else if (depth == 0 && code == kCodeAccount) {
+        t.acct_off = pos;
+        t.acct_len = size;
       }
     } else if (type == 18) {  // PATHSET
       bool empty = true;

@@ -398,6 +398,97 @@ def tx_blob_prepare_device(blobs, offsets, lengths, tx_ids=True, stream=None, ki
     return out
 
 
+# ---- signer authority: account IDs and the master-key match ----
+
+ACCOUNT_ID_BYTES = N.STL_ACCOUNT_ID_BYTES
+SIGNER_NOT_MASTER, SIGNER_MASTER, SIGNER_UNDECIDED = (N.STL_SIGNER_NOT_MASTER, N.STL_SIGNER_MASTER,
+                                                      N.STL_SIGNER_UNDECIDED)
+
+
+def _check_ids(n, **ts):
+    """The kernels write raw bytes: every ID buffer is uint8 and (n, 20)."""
+    import torch
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name} must be torch.uint8")
+        if tuple(t.shape) != (n, ACCOUNT_ID_BYTES):
+            raise ValueError(f"{name} must be (n, 20) bytes")
+
+
+def account_id_batch(pk):
+    """stl_account_id_batch: Hash160 of n 32-byte account public keys (host
+    memory; RippleAddress::getAccountID) -> (n, 20) uint8."""
+    pk = np.ascontiguousarray(pk)
+    if pk.dtype != np.uint8 or pk.ndim != 2 or pk.shape[1] != 32:
+        raise ValueError("pk must be (n, 32) uint8")
+    n = pk.shape[0]
+    out = np.zeros((n, ACCOUNT_ID_BYTES), dtype=np.uint8)
+    N.check(N.load().stl_account_id_batch(_buf(pk), n, _buf(out)), "stl_account_id_batch")
+    return out
+
+
+def account_id_batch_device(pk, out=None, stream=None):
+    """pk (n, 32) uint8 CUDA tensor -> (n, 20) uint8 account IDs (async on
+    ``stream``)."""
+    import torch
+    if pk.dtype != torch.uint8 or pk.dim() != 2 or pk.shape[1] != 32:
+        raise ValueError("pk must be (n, 32) torch.uint8")
+    n = pk.shape[0]
+    if out is None:
+        out = torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=pk.device)
+    _check_ids(n, out=out)
+    for t in (pk, out):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("device entry point needs contiguous CUDA tensors")
+    N.check(N.load().stl_account_id_batch_device(ctypes.c_void_p(pk.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                                 _stream_ptr(stream)), "stl_account_id_batch_device")
+    return out
+
+
+def tx_blob_signer_batch_device(blobs, offsets, lengths, accounts=True, stream=None, out_signer_id=None,
+                                out_account=None, out_authority=None):
+    """stl_tx_blob_signer_batch_device: serialized transactions in HBM (as
+    tx_blob_prepare_device takes them) -> dict of signer_id (n, 20), account
+    (n, 20), or None without ``accounts``, and authority (n,) -- SIGNER_MASTER
+    / SIGNER_NOT_MASTER / SIGNER_UNDECIDED, see include/stl.h."""
+    import torch
+    n = offsets.shape[0]
+    dev = blobs.device
+    signer = torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=dev) if out_signer_id is None \
+        else out_signer_id
+    account = out_account if out_account is not None else (
+        torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=dev) if accounts else None)
+    authority = torch.empty((n,), dtype=torch.uint8, device=dev) if out_authority is None else out_authority
+    _check_ids(n, out_signer_id=signer, out_account=account)
+    if authority.dtype != torch.uint8 or tuple(authority.shape) != (n,):
+        raise ValueError("out_authority must be (n,) torch.uint8")
+    if blobs.dtype != torch.uint8:
+        raise ValueError("blobs must be torch.uint8")
+    _check_rows(blobs, offsets, lengths, signer, account, authority)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    N.check(N.load().stl_tx_blob_signer_batch_device(p(blobs), p(offsets), p(lengths), n, p(signer), p(account),
+                                                     p(authority), _stream_ptr(stream)),
+            "stl_tx_blob_signer_batch_device")
+    return {"signer_id": signer, "account": account, "authority": authority}
+
+
+def tx_blob_signer_batch(blobs, accounts=True):
+    """stl_tx_blob_signer_batch: who signed each serialized transaction (list
+    of bytes).  Returns (signer_id (n, 20), account (n, 20) or None, authority
+    uint8[n])."""
+    n = len(blobs)
+    buf, offs, lens = _pack(blobs)
+    signer = np.zeros((max(n, 1), ACCOUNT_ID_BYTES), dtype=np.uint8)
+    account = np.zeros((max(n, 1), ACCOUNT_ID_BYTES), dtype=np.uint8) if accounts else None
+    authority = np.zeros(max(n, 1), dtype=np.uint8)
+    N.check(N.load().stl_tx_blob_signer_batch(_buf(buf), _buf(offs), _buf(lens), n, _buf(signer),
+                                              _buf(account) if accounts else None, _buf(authority)),
+            "stl_tx_blob_signer_batch")
+    return signer[:n], (account[:n] if accounts else None), authority[:n]
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
