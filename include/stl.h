@@ -283,9 +283,11 @@ int stl_signed_blob_verify_batch_device(uint32_t kind, const uint8_t *d_blobs, c
  * account's RegularKey from ledger state.  getAccountID() of an account public
  * key is Hash160(key) = RIPEMD160(SHA256(key)) (RippleAddress.cpp:361-363,
  * HashUtilities.cpp:22-29).  These calls compute the IDs and the first
- * comparison for a whole batch; the RegularKey comparison stays with the
- * caller.  Single device; the host forms upload, run the device form and copy
- * back.  A failure is a negative code, never a verdict. */
+ * comparison for a whole batch from the blobs alone; the RegularKey comparison
+ * needs ledger state, which the account directory below (stl_acctdir_*) keeps
+ * on the device: its stl_acctdir_tx_blob_authority* gives checkSig's whole
+ * verdict per row.  Single device; the host forms upload, run the device form
+ * and copy back.  A failure is a negative code, never a verdict. */
 #define STL_ACCOUNT_ID_BYTES 20u
 /* Hash160 of n 32-byte account public keys = RippleAddress::getAccountID
  * (RippleAddress.cpp:361-363).  account_id: n*20 bytes, the digest bytes in
@@ -294,7 +296,7 @@ int stl_signed_blob_verify_batch_device(uint32_t kind, const uint8_t *d_blobs, c
 int stl_account_id_batch(const uint8_t *pk, size_t n, uint8_t *account_id); /* host memory, synchronous */
 int stl_account_id_batch_device(const uint8_t *d_pk, size_t n, uint8_t *d_account_id, void *stream);
 
-#define STL_SIGNER_NOT_MASTER 0u /* Hash160(SigningPubKey) != Account: the caller checks RegularKey (ledger state) */
+#define STL_SIGNER_NOT_MASTER 0u /* Hash160(SigningPubKey) != Account: RegularKey decides (ledger state: stl_acctdir_*) */
 #define STL_SIGNER_MASTER 1u     /* == Account: Transactor::checkSig's first branch */
 #define STL_SIGNER_UNDECIDED 2u  /* row is not STL_TX_OK, or Account is not 20 bytes: the caller's own path */
 /* Serialized transactions as stl_tx_blob_verify_batch takes them.  d_signer_id: n*20; d_account: n*20 or NULL;
@@ -664,6 +666,96 @@ int stl_keyset_signed_blob_verify_batch_device(stl_keyset *ks, uint32_t kind, co
  * (STL_KEYSET_BASE: the base point's table) copied to host memory, row_bytes / 4 words each. */
 int stl_debug_keyset_rows(const stl_keyset *ks, uint32_t key, uint32_t first_row, uint32_t nrows,
                           uint32_t *out_words);
+
+/* ---- account directory: Transactor::checkSig's verdict per row ----
+ * checkSig (Transactor.cpp:151-180, mHasAuthKey set at :326) decides from three fields of the
+ * account root:
+ *   signer == Account                          -> lsfDisableMaster ? tefMASTER_DISABLED : tesSUCCESS
+ *   else hasRegularKey && signer == RegularKey -> tesSUCCESS
+ *   else hasRegularKey                         -> tefBAD_AUTH
+ *   else                                       -> temBAD_AUTH_MASTER
+ * and without an account root the transactor has stopped before (:312-320).  A directory keeps those
+ * fields on the device, keyed by account ID and updatable per ledger, so the pass that walks the blob
+ * and hashes the signing key (stl_tx_blob_signer_batch_device) gives the final answer: one byte per
+ * row, and nothing else need go back to the host.
+ * THE ANSWER IS A SNAPSHOT: checkSig against the account state as last upserted.  A SetRegularKey or
+ * AccountSet earlier in the same apply order changes the account, so the caller re-decides the rows
+ * whose account an earlier transaction of the set touched.
+ * Device: a directory lives on one device, the calling thread's current device at creation, like a
+ * keyset; a call on another device, or with a handle that is not live, is STL_EINVAL.  It holds
+ * `bytes` of device memory: 48 B per account of capacity plus at least 16 B of slots (a hash map at a
+ * load of 1/4 at most), and while it has been upserted to, a staging buffer of 52 B per row of the
+ * largest batch.
+ * Concurrency: the caller must not run stl_acctdir_upsert concurrently with lookups (lookup,
+ * tx_blob_authority) on the same directory, work still in flight on a stream included, nor destroy
+ * a directory with calls in flight on other threads.  Lookups may run concurrently with each other.
+ * A failure is a negative code, never a verdict. */
+#define STL_ACCT_HAS_REGULAR_KEY 0x1u   /* sfRegularKey present */
+#define STL_ACCT_MASTER_DISABLED 0x2u   /* lsfDisableMaster */
+#define STL_ACCT_ABSENT 0x4u            /* upsert: the account root no longer exists */
+#define STL_ACCT_NOT_FOUND 0xFFu        /* lookup: not in the directory, or ABSENT */
+#define STL_ACCTDIR_MAX_ACCOUNTS 16777216u
+#define STL_AUTH_MASTER 0u            /* tesSUCCESS, mSigMaster */
+#define STL_AUTH_REGULAR 1u           /* tesSUCCESS by RegularKey */
+#define STL_AUTH_MASTER_DISABLED 2u   /* tefMASTER_DISABLED */
+#define STL_AUTH_BAD_AUTH 3u          /* tefBAD_AUTH */
+#define STL_AUTH_BAD_AUTH_MASTER 4u   /* temBAD_AUTH_MASTER */
+#define STL_AUTH_NO_ACCOUNT 5u        /* no such account in the directory (terNO_ACCOUNT is the caller's call) */
+#define STL_AUTH_UNDECIDED 6u         /* row not STL_TX_OK, or Account not 20 bytes */
+typedef struct stl_acctdir stl_acctdir;
+typedef struct stl_acctdir_info {
+  uint32_t struct_size;   /* sizeof(stl_acctdir_info) */
+  uint32_t capacity;      /* records the directory has room for */
+  uint32_t records;       /* records in use: accounts ever upserted (ABSENT ones included), plus any lost
+                             to a failed upsert */
+  uint32_t slots;         /* of the hash map: the power of two >= 4 * capacity */
+  uint32_t longest_probe; /* longest probe sequence an insert has walked */
+  int32_t device;         /* HIP device ordinal */
+  uint64_t bytes;         /* device memory of slots and records */
+  uint64_t seed;          /* of the map's hash */
+} stl_acctdir_info;
+/* capacity in 1..STL_ACCTDIR_MAX_ACCOUNTS; seed of the map's hash, 0: chosen at random (so account
+ * IDs cannot be made to collide).  Synchronous.  STL_OK and *out, or a negative code and *out = NULL. */
+int stl_acctdir_create(uint32_t capacity, uint64_t seed, stl_acctdir **out);
+/* Waits for the device, then frees the directory.  NULL, a destroyed handle and a handle from before
+ * stl_shutdown (which frees every directory) are ignored. */
+void stl_acctdir_destroy(stl_acctdir *dir);
+int stl_acctdir_get_info(const stl_acctdir *dir, stl_acctdir_info *out);
+/* Sets m accounts' state: account_id m*20 bytes, flags m bytes (STL_ACCT_HAS_REGULAR_KEY,
+ * STL_ACCT_MASTER_DISABLED, STL_ACCT_ABSENT; any other bit is STL_EINVAL), regular_key m*20 bytes, read
+ * only in rows with HAS_REGULAR_KEY (NULL allowed when no row has it, else STL_EINVAL).  Host memory,
+ * synchronous.  The batch's IDs are made distinct on the host: the last occurrence of an ID wins.  An
+ * account not yet in the directory takes one record, for good: STL_ACCT_ABSENT keeps the record, and
+ * later lookups say not found.  When records + distinct IDs of the batch > capacity the call is
+ * refused with STL_ENOMEM before any device work (the IDs already present count too: the host does
+ * not know them), and the directory is unchanged.
+ * A call that fails after it started device work (STL_EHIP, or STL_ENOMEM for its staging buffer) may
+ * have applied any part of the batch, and may have used up to m records of capacity; applying the
+ * same batch again completes it.  Lookups never see anything but the old or the new state of a whole
+ * account. */
+int stl_acctdir_upsert(stl_acctdir *dir, const uint8_t *account_id, const uint8_t *flags,
+                       const uint8_t *regular_key, size_t m);
+/* The device calls: device memory, asynchronous on `stream`.  Before any device work: a NULL
+ * required pointer, an ID array (d_account_id, d_regular_key, d_signer_id, d_account) that is not
+ * 4-byte aligned, or n > 0xffffffc0 is STL_EINVAL; n == 0 is STL_OK; without a device STL_ENODEV.
+ * The bare map: d_flags[i] = the flags byte of d_account_id[20 i ..], or STL_ACCT_NOT_FOUND (never
+ * upserted, or ABSENT); d_regular_key (n*20, or NULL): its RegularKey, zero unless HAS_REGULAR_KEY.
+ * Exactly n and n*20 bytes are written. */
+int stl_acctdir_lookup_device(stl_acctdir *dir, const uint8_t *d_account_id, size_t n, uint8_t *d_flags,
+                              uint8_t *d_regular_key, void *stream);
+/* Rows, d_signer_id (n*20, or NULL) and d_account (n*20, or NULL) as stl_tx_blob_signer_batch_device
+ * takes and writes them, bit for bit.  d_authority[i]: for a row that call decides (STL_TX_OK with a
+ * 20-byte Account) the STL_AUTH_* verdict of the branches above on the Account's entry, the master
+ * branch first (a master-signed row on a MASTER_DISABLED account is MASTER_DISABLED whatever its
+ * RegularKey); STL_AUTH_UNDECIDED for every other row.  One kernel: no workspace, no host wait. */
+int stl_acctdir_tx_blob_authority_device(stl_acctdir *dir, const uint8_t *d_blobs, const uint64_t *d_offset,
+                                         const uint32_t *d_len, size_t n, uint8_t *d_signer_id,
+                                         uint8_t *d_account, uint8_t *d_authority, void *stream);
+/* Host form: host memory, synchronous (upload, the device form, copy back); signer_id and account
+ * may be NULL. */
+int stl_acctdir_tx_blob_authority(stl_acctdir *dir, const uint8_t *blobs, const uint64_t *offset,
+                                  const uint32_t *len, size_t n, uint8_t *signer_id, uint8_t *account,
+                                  uint8_t *authority);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,20 @@ STL_SIGNER_NOT_MASTER = 0
 STL_SIGNER_MASTER = 1
 STL_SIGNER_UNDECIDED = 2
 
+# account directory (stl_acctdir_*)
+STL_ACCT_HAS_REGULAR_KEY = 0x1
+STL_ACCT_MASTER_DISABLED = 0x2
+STL_ACCT_ABSENT = 0x4
+STL_ACCT_NOT_FOUND = 0xFF
+STL_ACCTDIR_MAX_ACCOUNTS = 16777216
+STL_AUTH_MASTER = 0
+STL_AUTH_REGULAR = 1
+STL_AUTH_MASTER_DISABLED = 2
+STL_AUTH_BAD_AUTH = 3
+STL_AUTH_BAD_AUTH_MASTER = 4
+STL_AUTH_NO_ACCOUNT = 5
+STL_AUTH_UNDECIDED = 6
+
 # Every entry point include/stl.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U8P = ctypes.c_void_p
@@ -145,6 +159,14 @@ SYMBOLS = [
     ("stl_account_id_batch_device", ctypes.c_int, [_U8P, ctypes.c_size_t, _U8P, _P]),
     ("stl_tx_blob_signer_batch_device", ctypes.c_int, [_U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),
     ("stl_tx_blob_signer_batch", ctypes.c_int, [_U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P]),
+    ("stl_acctdir_create", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint64, _P]),
+    ("stl_acctdir_destroy", None, [_P]),
+    ("stl_acctdir_get_info", ctypes.c_int, [_P, _P]),
+    ("stl_acctdir_upsert", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t]),
+    ("stl_acctdir_lookup_device", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _U8P, _U8P, _P]),
+    ("stl_acctdir_tx_blob_authority_device", ctypes.c_int,
+     [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),
+    ("stl_acctdir_tx_blob_authority", ctypes.c_int, [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -33,6 +33,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <random>
 #include <set>
 #include <thread>
 #include <vector>
@@ -42,6 +43,8 @@
 #include "stl_keycache.h"
 #include "stl_keyset.h"
 #include "stl_keyset_map.h"
+#include "stl_acctdir.h"
+#include "stl_acctdir_core.h"
 #include "stl_signer.h"
 
 namespace {
@@ -1474,6 +1477,8 @@ void keysets_release_all() {
   while (!g_keysets.empty()) keyset_free_locked(const_cast<stl_keyset*>(*g_keysets.begin()));
 }
 
+void acctdirs_release_all();  // the account directories, further down
+
 int check_keyset_flags(uint32_t flags) {
   return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_DEBUG_RAW_PREDICATE)) ? STL_EINVAL : STL_OK;
 }
@@ -1583,6 +1588,7 @@ int stl_init(const stl_config* cfg) {
 void stl_shutdown(void) {
   stl_comm_destroy();
   keysets_release_all();
+  acctdirs_release_all();
   DeviceGuard guard;
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto& d : g_devs) {
@@ -3042,6 +3048,246 @@ int stl_tx_blob_signer_batch(const uint8_t* blobs, const uint64_t* offset, const
     return span.finish(rc);
   }
   std::memcpy(signer_id, host.data(), idb);
+  if (account) std::memcpy(account, host.data() + idb, idb);
+  std::memcpy(authority, host.data() + 2 * idb, n);
+  return span.finish(STL_OK);
+}
+
+}  // extern "C"
+
+// ---- account directory: Transactor::checkSig's verdict per row (stl_acctdir.hip) ----
+// One directory: on one device the slots, the records and two words of
+// bookkeeping (stl_acctdir.h AcctDirDev), plus the staging buffer of upsert.
+// The record count is the device's word; `records` is the host's copy, read
+// back at the end of every upsert (count_stale: that read has yet to succeed).
+struct stl_acctdir {
+  int ordinal = -1;
+  uint32_t capacity = 0, nslots = 0;
+  uint64_t seed = 0;
+  uint32_t records = 0, longest_probe = 0;
+  bool count_stale = false;
+  DevBuf slots, recs, meta, stage;
+  stl::AcctDirDev dev() const {
+    return stl::AcctDirDev{static_cast<uint32_t*>(slots.p), static_cast<uint32_t*>(recs.p),
+                           static_cast<uint32_t*>(meta.p), nslots - 1, capacity, seed};
+  }
+  size_t bytes() const { return (size_t)nslots * 4 + (size_t)capacity * stl::kAdRecWords * 4; }
+};
+
+namespace {
+// The live directories; g_ad_mu as g_ks_mu for the keysets: held while a call
+// looks its handle up and enqueues its kernels, and while one is destroyed.
+// Lock order: g_ad_mu before a device's mu.
+std::mutex g_ad_mu;
+std::set<const stl_acctdir*> g_acctdirs;
+
+void acctdir_free_locked(stl_acctdir* dir) {
+  g_acctdirs.erase(dir);
+  DeviceGuard guard;
+  if (hipSetDevice(dir->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
+  dir->slots.release();
+  dir->recs.release();
+  dir->meta.release();
+  dir->stage.release();
+  delete dir;
+}
+
+void acctdirs_release_all() {
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  while (!g_acctdirs.empty()) acctdir_free_locked(const_cast<stl_acctdir*>(*g_acctdirs.begin()));
+}
+
+// The live directory of a handle on the calling thread's device (g_ad_mu
+// held), by keyset_for_call's rule; without a device STL_ENODEV comes first.
+int acctdir_for_call(const stl_acctdir* dir, Device** d) {
+  STL_RC(device_for_call(d));
+  if (!dir || !g_acctdirs.count(dir)) return STL_EINVAL;
+  return (*d)->ordinal == dir->ordinal ? STL_OK : STL_EINVAL;
+}
+
+// meta[0 .. 2) -> the host's copy.  Not counted by the fault injection: it
+// also runs on upsert's failure path.
+bool acctdir_read_meta(stl_acctdir& dir) {
+  uint32_t m[2] = {0, 0};
+  if (hipMemcpy(m, dir.meta.p, sizeof(m), hipMemcpyDeviceToHost) != hipSuccess) {
+    dir.count_stale = true;
+    return false;
+  }
+  dir.records = std::min(m[0], dir.capacity);
+  dir.longest_probe = m[1];
+  dir.count_stale = false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int stl_acctdir_create(uint32_t capacity, uint64_t seed, stl_acctdir** out) {
+  if (out) *out = nullptr;
+  if (!out || capacity == 0 || capacity > STL_ACCTDIR_MAX_ACCOUNTS) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  while (seed == 0) {
+    std::random_device rd;
+    seed = ((uint64_t)rd() << 32) ^ rd();
+  }
+  std::unique_ptr<stl_acctdir> dir(new stl_acctdir());
+  dir->ordinal = d->ordinal;
+  dir->capacity = capacity;
+  dir->nslots = stl::acctdir_slots(capacity);
+  dir->seed = seed;
+  DeviceGuard guard;
+  auto go = [&]() -> int {
+    std::lock_guard<std::mutex> lk(d->mu);
+    STL_TRY(hipSetDevice(d->ordinal));
+    STL_RC(dir->slots.ensure((size_t)dir->nslots * 4));
+    STL_RC(dir->recs.ensure((size_t)capacity * stl::kAdRecWords * 4));
+    STL_RC(dir->meta.ensure(8));
+    STL_TRY(hipMemsetAsync(dir->slots.p, 0xFF, (size_t)dir->nslots * 4, d->stream));
+    STL_TRY(hipMemsetAsync(dir->recs.p, 0, (size_t)capacity * stl::kAdRecWords * 4, d->stream));
+    STL_TRY(hipMemsetAsync(dir->meta.p, 0, 8, d->stream));
+    STL_TRY(hipStreamSynchronize(d->stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    dir->slots.release();
+    dir->recs.release();
+    dir->meta.release();
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  g_acctdirs.insert(dir.get());
+  *out = dir.release();
+  return STL_OK;
+}
+
+void stl_acctdir_destroy(stl_acctdir* dir) {
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  if (dir && g_acctdirs.count(dir)) acctdir_free_locked(dir);
+}
+
+int stl_acctdir_get_info(const stl_acctdir* dir, stl_acctdir_info* out) {
+  if (!out || out->struct_size != sizeof(stl_acctdir_info)) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  if (!dir || !g_acctdirs.count(dir)) return STL_EINVAL;
+  if (dir->count_stale) {
+    DeviceGuard guard;
+    if (hipSetDevice(dir->ordinal) != hipSuccess || !acctdir_read_meta(*const_cast<stl_acctdir*>(dir))) return STL_EHIP;
+  }
+  out->capacity = dir->capacity;
+  out->records = dir->records;
+  out->slots = dir->nslots;
+  out->longest_probe = dir->longest_probe;
+  out->device = dir->ordinal;
+  out->bytes = dir->bytes();
+  out->seed = dir->seed;
+  return STL_OK;
+}
+
+int stl_acctdir_upsert(stl_acctdir* dir, const uint8_t* account_id, const uint8_t* flags, const uint8_t* regular_key,
+                       size_t m) {
+  if (m == 0) return STL_OK;
+  if (!dir || !account_id || !flags || m > 0xffffffc0ull) return STL_EINVAL;
+  std::vector<uint32_t> staged;
+  if (!stl::acctdir_stage(account_id, flags, regular_key, m, staged)) return STL_EINVAL;
+  const size_t distinct = staged.size() / stl::kAdRecWords;
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  Device* d = nullptr;
+  STL_RC(acctdir_for_call(dir, &d));
+  DeviceGuard guard;
+  std::lock_guard<std::mutex> dl(d->mu);
+  if (dir->count_stale && !acctdir_read_meta(*dir)) return STL_EHIP;
+  if ((size_t)dir->records + distinct > dir->capacity) return STL_ENOMEM;  // before any device work
+  const size_t rec_bytes = distinct * stl::kAdRecWords * 4;
+  auto go = [&]() -> int {
+    STL_TRY(hipSetDevice(d->ordinal));
+    STL_RC(dir->stage.ensure(rec_bytes + distinct * 4));
+    uint32_t* d_staged = static_cast<uint32_t*>(dir->stage.p);
+    uint32_t* d_new = d_staged + distinct * stl::kAdRecWords;
+    STL_TRY(hipMemcpyAsync(d_staged, staged.data(), rec_bytes, hipMemcpyHostToDevice, d->stream));
+    STL_TRY(stl::launch_acctdir_find(dir->dev(), d_staged, (uint32_t)distinct, d_new, d->stream));
+    STL_TRY(stl::launch_acctdir_claim(dir->dev(), d_staged, (uint32_t)distinct, d_new, d->stream));
+    STL_TRY(hipStreamSynchronize(d->stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) (void)hipStreamSynchronize(d->stream);  // nothing may still read `staged`
+  const bool read = acctdir_read_meta(*dir);       // the count moved even where the call failed
+  return rc ? rc : (read ? STL_OK : STL_EHIP);
+}
+
+int stl_acctdir_lookup_device(stl_acctdir* dir, const uint8_t* d_account_id, size_t n, uint8_t* d_flags,
+                              uint8_t* d_regular_key, void* stream) {
+  if (n == 0) return STL_OK;
+  if (!dir || !d_account_id || !d_flags || n > 0xffffffc0ull) return STL_EINVAL;
+  if (((uintptr_t)d_account_id & 3u) != 0 || ((uintptr_t)d_regular_key & 3u) != 0) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  Device* d = nullptr;
+  STL_RC(acctdir_for_call(dir, &d));
+  STL_TRY(stl::launch_acctdir_lookup(dir->dev(), d_account_id, (uint32_t)n, d_flags, d_regular_key,
+                                     static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_acctdir_tx_blob_authority_device(stl_acctdir* dir, const uint8_t* d_blobs, const uint64_t* d_offset,
+                                         const uint32_t* d_len, size_t n, uint8_t* d_signer_id, uint8_t* d_account,
+                                         uint8_t* d_authority, void* stream) {
+  if (n == 0) return STL_OK;
+  if (!dir || !d_blobs || !d_offset || !d_len || !d_authority || n > 0xffffffc0ull) return STL_EINVAL;
+  if (((uintptr_t)d_signer_id & 3u) != 0 || ((uintptr_t)d_account & 3u) != 0) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  Device* d = nullptr;
+  STL_RC(acctdir_for_call(dir, &d));
+  STL_TRY(stl::launch_acctdir_authority(dir->dev(), d_blobs, d_offset, d_len, (uint32_t)n, d_signer_id, d_account,
+                                        d_authority, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_acctdir_tx_blob_authority(stl_acctdir* dir, const uint8_t* blobs, const uint64_t* offset, const uint32_t* len,
+                                  size_t n, uint8_t* signer_id, uint8_t* account, uint8_t* authority) {
+  if (n == 0) return STL_OK;
+  if (!dir || !blobs || !offset || !len || !authority || n > 0xffffffc0ull) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_ad_mu);
+  Device* dp = nullptr;
+  STL_RC(acctdir_for_call(dir, &dp));
+  Device& d = *dp;
+  CallSpan span{"stl_acctdir_tx_blob_authority", n};
+  DeviceGuard guard;
+  std::lock_guard<std::mutex> dl(d.mu);
+  std::vector<uint64_t> roff, row_end;
+  uint64_t base = 0, bytes = 0;
+  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
+  const size_t idb = n * STL_ACCOUNT_ID_BYTES;
+  std::vector<uint8_t> host(2 * idb + n);  // signer IDs, accounts, authority
+  auto go = [&]() -> int {
+    STL_TRY(hipSetDevice(d.ordinal));
+    STL_RC(d.pre.ensure(bytes + 16));
+    STL_RC(d.off.ensure(n * 8));
+    STL_RC(d.len.ensure(n * 4));
+    STL_RC(d.msg.ensure(idb));
+    STL_RC(d.txid.ensure(idb));
+    STL_RC(d.status.ensure(n));
+    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(stl::launch_acctdir_authority(
+        dir->dev(), static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
+        static_cast<const uint32_t*>(d.len.p), (uint32_t)n, signer_id ? static_cast<uint8_t*>(d.msg.p) : nullptr,
+        account ? static_cast<uint8_t*>(d.txid.p) : nullptr, static_cast<uint8_t*>(d.status.p), d.stream));
+    if (signer_id) STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, idb, hipMemcpyDeviceToHost, d.stream));
+    if (account) STL_TRY(hipMemcpyAsync(host.data() + idb, d.txid.p, idb, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipMemcpyAsync(host.data() + 2 * idb, d.status.p, n, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {  // nothing may still read the caller's rows or write host
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  if (signer_id) std::memcpy(signer_id, host.data(), idb);
   if (account) std::memcpy(account, host.data() + idb, idb);
   std::memcpy(authority, host.data() + 2 * idb, n);
   return span.finish(STL_OK);

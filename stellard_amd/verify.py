@@ -489,6 +489,149 @@ def tx_blob_signer_batch(blobs, accounts=True):
     return signer[:n], (account[:n] if accounts else None), authority[:n]
 
 
+# ---- account directory (stl_acctdir_*) ----
+
+ACCT_HAS_REGULAR_KEY, ACCT_MASTER_DISABLED, ACCT_ABSENT, ACCT_NOT_FOUND = (
+    N.STL_ACCT_HAS_REGULAR_KEY, N.STL_ACCT_MASTER_DISABLED, N.STL_ACCT_ABSENT, N.STL_ACCT_NOT_FOUND)
+ACCTDIR_MAX_ACCOUNTS = N.STL_ACCTDIR_MAX_ACCOUNTS
+(AUTH_MASTER, AUTH_REGULAR, AUTH_MASTER_DISABLED, AUTH_BAD_AUTH, AUTH_BAD_AUTH_MASTER, AUTH_NO_ACCOUNT,
+ AUTH_UNDECIDED) = (N.STL_AUTH_MASTER, N.STL_AUTH_REGULAR, N.STL_AUTH_MASTER_DISABLED, N.STL_AUTH_BAD_AUTH,
+                    N.STL_AUTH_BAD_AUTH_MASTER, N.STL_AUTH_NO_ACCOUNT, N.STL_AUTH_UNDECIDED)
+
+
+class AcctDirInfo(ctypes.Structure):
+    """stl_acctdir_info (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("capacity", ctypes.c_uint32), ("records", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32), ("longest_probe", ctypes.c_uint32), ("device", ctypes.c_int32),
+                ("bytes", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
+
+
+class AccountDirectory:
+    """A device-resident snapshot of the account-root fields Transactor::checkSig
+    reads (stl_acctdir_create), keyed by account ID and updated per ledger with
+    ``upsert``; ``tx_blob_authority_device`` gives checkSig's verdict (AUTH_*)
+    per serialized transaction against the state as last upserted.
+
+        with AccountDirectory(capacity) as d:
+            d.upsert(ids, flags, regular_keys)
+            out = d.tx_blob_authority_device(blobs, offsets, lengths)
+    """
+
+    def __init__(self, capacity, seed=0):
+        h = ctypes.c_void_p()
+        N.check(N.load().stl_acctdir_create(int(capacity), int(seed), ctypes.byref(h)), "stl_acctdir_create")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            N.load().stl_acctdir_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        i = AcctDirInfo(struct_size=ctypes.sizeof(AcctDirInfo))
+        N.check(N.load().stl_acctdir_get_info(self._h, ctypes.byref(i)), "stl_acctdir_get_info")
+        return {k: getattr(i, k) for k, _ in AcctDirInfo._fields_ if k != "struct_size"}
+
+    def upsert(self, account_id, flags, regular_key=None):
+        """Host arrays: account_id (m, 20) uint8, flags (m,) uint8 of ACCT_*
+        bits, regular_key (m, 20) uint8 (optional when no row has
+        ACCT_HAS_REGULAR_KEY).  Synchronous; the last occurrence of an ID wins."""
+        account_id = np.ascontiguousarray(account_id)
+        flags = np.ascontiguousarray(flags)
+        if account_id.dtype != np.uint8 or account_id.ndim != 2 or account_id.shape[1] != ACCOUNT_ID_BYTES:
+            raise ValueError("account_id must be (m, 20) uint8")
+        m = account_id.shape[0]
+        if flags.dtype != np.uint8 or flags.shape != (m,):
+            raise ValueError("flags must be (m,) uint8")
+        if regular_key is not None:
+            regular_key = np.ascontiguousarray(regular_key)
+            if regular_key.dtype != np.uint8 or regular_key.shape != (m, ACCOUNT_ID_BYTES):
+                raise ValueError("regular_key must be (m, 20) uint8")
+        N.check(N.load().stl_acctdir_upsert(self._h, _buf(account_id), _buf(flags),
+                                            _buf(regular_key) if regular_key is not None else None, m),
+                "stl_acctdir_upsert")
+
+    def lookup_device(self, account_id, regular_keys=True, stream=None, out_flags=None, out_regular_key=None):
+        """account_id (n, 20) uint8 CUDA tensor -> dict of flags (n,) -- the
+        ACCT_* bits, or ACCT_NOT_FOUND -- and regular_key (n, 20), or None
+        without ``regular_keys`` (async on ``stream``)."""
+        import torch
+        if account_id.dtype != torch.uint8:
+            raise ValueError("account_id must be torch.uint8")
+        if account_id.dim() != 2 or account_id.shape[1] != ACCOUNT_ID_BYTES:
+            raise ValueError("account_id must be (n, 20) bytes")
+        n = account_id.shape[0]
+        dev = account_id.device
+        flags = torch.empty((n,), dtype=torch.uint8, device=dev) if out_flags is None else out_flags
+        rk = out_regular_key if out_regular_key is not None else (
+            torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=dev) if regular_keys else None)
+        _check_ids(n, out_regular_key=rk)
+        if flags.dtype != torch.uint8 or tuple(flags.shape) != (n,):
+            raise ValueError("out_flags must be (n,) torch.uint8")
+        for t in (account_id, flags, rk):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_acctdir_lookup_device(self._h, p(account_id), n, p(flags), p(rk), _stream_ptr(stream)),
+                "stl_acctdir_lookup_device")
+        return {"flags": flags, "regular_key": rk}
+
+    def tx_blob_authority_device(self, blobs, offsets, lengths, signer_ids=True, accounts=True, stream=None,
+                                 out_signer_id=None, out_account=None, out_authority=None):
+        """stl_acctdir_tx_blob_authority_device: serialized transactions in HBM
+        (as tx_blob_signer_batch_device takes them) -> dict of signer_id
+        (n, 20) or None, account (n, 20) or None, and authority (n,) of AUTH_*."""
+        import torch
+        n = offsets.shape[0]
+        dev = blobs.device
+        signer = out_signer_id if out_signer_id is not None else (
+            torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=dev) if signer_ids else None)
+        account = out_account if out_account is not None else (
+            torch.empty((n, ACCOUNT_ID_BYTES), dtype=torch.uint8, device=dev) if accounts else None)
+        authority = torch.empty((n,), dtype=torch.uint8, device=dev) if out_authority is None else out_authority
+        _check_ids(n, out_signer_id=signer, out_account=account)
+        if authority.dtype != torch.uint8 or tuple(authority.shape) != (n,):
+            raise ValueError("out_authority must be (n,) torch.uint8")
+        if blobs.dtype != torch.uint8:
+            raise ValueError("blobs must be torch.uint8")
+        _check_rows(blobs, offsets, lengths, signer, account, authority)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_acctdir_tx_blob_authority_device(
+            self._h, p(blobs), p(offsets), p(lengths), n, p(signer), p(account), p(authority), _stream_ptr(stream)),
+            "stl_acctdir_tx_blob_authority_device")
+        return {"signer_id": signer, "account": account, "authority": authority}
+
+    def tx_blob_authority(self, blobs, signer_ids=True, accounts=True):
+        """stl_acctdir_tx_blob_authority: checkSig's verdict for each
+        serialized transaction (list of bytes).  Returns (signer_id (n, 20) or
+        None, account (n, 20) or None, authority uint8[n])."""
+        n = len(blobs)
+        buf, offs, lens = _pack(blobs)
+        signer = np.zeros((max(n, 1), ACCOUNT_ID_BYTES), dtype=np.uint8) if signer_ids else None
+        account = np.zeros((max(n, 1), ACCOUNT_ID_BYTES), dtype=np.uint8) if accounts else None
+        authority = np.zeros(max(n, 1), dtype=np.uint8)
+        N.check(N.load().stl_acctdir_tx_blob_authority(
+            self._h, _buf(buf), _buf(offs), _buf(lens), n, _buf(signer) if signer_ids else None,
+            _buf(account) if accounts else None, _buf(authority)), "stl_acctdir_tx_blob_authority")
+        return (signer[:n] if signer_ids else None), (account[:n] if accounts else None), authority[:n]
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
