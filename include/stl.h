@@ -757,6 +757,90 @@ int stl_acctdir_tx_blob_authority(stl_acctdir *dir, const uint8_t *blobs, const 
                                   const uint32_t *len, size_t n, uint8_t *signer_id, uint8_t *account,
                                   uint8_t *authority);
 
+/* ---- verified-ID cache: rows already accepted skip the Ed25519 verify ----
+ * stellard verifies the same transaction several times: on ingest, when a peer's proposed set is
+ * acquired, at ledger close and on every retry pass, and for held transactions.  Its answer is
+ * HashRouter's SF_SIGGOOD flag, keyed by transaction ID (IHashRouter.h:27-33).  A sigcache is the
+ * device-resident counterpart: the IDs of the rows libstl's own verify has accepted, in device
+ * memory from one call to the next.  stl_sigcache_signed_blob_verify_batch_device runs the blob pass
+ * (parse, both hashes) on every row, probes the cache with each STL_TX_OK row's ID, gives a row that
+ * is found accept bit 1 and sends only the others through the per-signature kernels; the rows those
+ * accept are inserted.  The ID (SHA512Half("TXN\0" || blob), for a validation SHA512Half(blob))
+ * commits to every byte of the blob, and the accept bit is a function of the blob and the predicate
+ * alone, so a hit is the verdict: it never goes stale and needs no ledger state.  Only accepts are
+ * kept; a rejected, deferred or malformed row is decided anew in every call.
+ * CONTRACT: for every input, cache state and interleaving with other calls on the same cache,
+ * d_bitmap_words, d_status and d_id are what stl_signed_blob_verify_batch_device writes for the same
+ * rows, kind and flags.
+ * Binding: a cache is made for one blob kind and one accept predicate,
+ * flags & (STL_POLICY_MASK | STL_DEBUG_RAW_PREDICATE).  A verify call with another predicate is
+ * STL_EINVAL before any device work; the flags that do not change bits (STL_FULL_LENGTH,
+ * STL_DEDUP_KEYS, STL_NO_AUTO_DEDUP, STL_ONE_LANE) are the call's own.
+ * Layout: 2^sets_log2 sets of one 128-byte line, 4 ways of a 32-byte ID, 128 << sets_log2 bytes in
+ * all; the set comes from a seeded hash of the ID.  A set that receives a fifth ID overwrites one:
+ * capacity is the only reason an ID leaves (no expiry), and stl_sigcache_clear the only other.
+ * While a set has received at most 4 distinct IDs since creation or clear all of them are present
+ * once the inserting work has completed (stl_sigcache_core.h states it exactly).
+ * Device: a cache lives on one device, the calling thread's current device at creation, like a
+ * keyset; a call on another device, or with a handle that is not live, is STL_EINVAL;
+ * stl_shutdown frees every cache.
+ * Concurrency: verify calls, lookups and clears on one cache may run concurrently from several
+ * threads and streams (a racing insert may or may not survive a clear; how soon one stream's
+ * inserts are seen by another only moves the hit rate).  Only destroy needs quiescence.
+ * A failure is a negative code, never a verdict; a failed call may leave out inserts, but never
+ * inserts an ID whose verify did not run. */
+#define STL_SIGCACHE_MAX_SETS_LOG2 24u /* 2 GiB */
+#define STL_SIGCACHE_WAYS 4u
+typedef struct stl_sigcache stl_sigcache;
+typedef struct stl_sigcache_info {
+  uint32_t struct_size; /* sizeof(stl_sigcache_info) */
+  uint32_t sets_log2;
+  uint32_t ways;        /* STL_SIGCACHE_WAYS */
+  uint32_t kind;        /* STL_BLOB_* */
+  uint32_t predicate;   /* flags & (STL_POLICY_MASK | STL_DEBUG_RAW_PREDICATE) */
+  int32_t device;       /* HIP device ordinal */
+  uint64_t bytes;       /* device memory of the sets: 128 << sets_log2 */
+  uint64_t seed;        /* of the set hash */
+} stl_sigcache_info;
+/* sets_log2 in 0..STL_SIGCACHE_MAX_SETS_LOG2; kind STL_BLOB_TRANSACTION or STL_BLOB_VALIDATION; flags:
+ * the predicate (the policy bit, STL_DEBUG_RAW_PREDICATE; STL_REQUIRE_S_LT_L is accepted), anything
+ * else is STL_EINVAL; seed of the set hash, 0: chosen at random (so a peer cannot grind IDs into one
+ * set).  Synchronous.  STL_OK and *out, or a negative code and *out = NULL. */
+int stl_sigcache_create(uint32_t sets_log2, uint32_t kind, uint32_t flags, uint64_t seed, stl_sigcache **out);
+/* Waits for the device, then frees the cache.  NULL, a destroyed handle and a handle from before
+ * stl_shutdown are ignored.  No call on the cache may be running on another thread. */
+void stl_sigcache_destroy(stl_sigcache *c);
+int stl_sigcache_get_info(const stl_sigcache *c, stl_sigcache_info *out);
+/* Empties the cache: a memset enqueued on `stream`, asynchronous. */
+int stl_sigcache_clear(stl_sigcache *c, void *stream);
+/* The bare probe: bit i of d_hit_words = the 32-byte ID d_id[32 i ..] is present.  Device memory,
+ * d_id 16-byte aligned, asynchronous on `stream`; ceil(n / 64) words are written whole (the last
+ * word's tail bits are zero). */
+int stl_sigcache_lookup_device(stl_sigcache *c, const uint8_t *d_id, size_t n, uint64_t *d_hit_words,
+                               void *stream);
+/* The cached checkSign of serialized objects in device memory; rows, d_bitmap_words, d_status and
+ * d_id (nullable, 16-byte aligned) as stl_signed_blob_verify_batch_device takes and writes them, the
+ * kind is the cache's.  flags: as that call's, with the cache's predicate.  *hits (nullable): the
+ * STL_TX_OK rows found in the cache; *verified (nullable): the STL_TX_OK rows that were not, which
+ * went through the per-signature kernels.  With every STL_TX_OK row a hit no per-signature kernel
+ * is launched.  Before any device work: a NULL required pointer, n > 0xffffffc0, an unknown flag
+ * bit, a misaligned d_id or another predicate than the cache's is STL_EINVAL; n == 0 is STL_OK.
+ * SYNCHRONISATION: the call waits once on `stream`, for its probe kernel (an event recorded behind
+ * the copy of the miss count) -- the host has to learn the miss count before it can size and launch
+ * the per-signature kernels.  Everything else is asynchronous: the gather of the misses, their
+ * verify, the scatter of their bits and, last, the insert; the outputs are complete when `stream`
+ * reaches the call's end.  The stream context holds the call's buffers: 164 B per row (132 B with
+ * d_id given), 128 B per miss. */
+int stl_sigcache_signed_blob_verify_batch_device(stl_sigcache *c, const uint8_t *d_blobs, const uint64_t *d_offset,
+                                                 const uint32_t *d_len, size_t n, uint64_t *d_bitmap_words,
+                                                 uint8_t *d_status, uint8_t *d_id, uint32_t flags, void *stream,
+                                                 size_t *hits, size_t *verified);
+/* Host form: host memory, synchronous (upload, the device form, copy back); accept_bitmap, status
+ * and id (nullable) as stl_signed_blob_verify_batch writes them. */
+int stl_sigcache_signed_blob_verify_batch(stl_sigcache *c, const uint8_t *blobs, const uint64_t *offset,
+                                          const uint32_t *len, size_t n, uint8_t *accept_bitmap, uint8_t *status,
+                                          uint8_t *id, uint32_t flags, size_t *hits, size_t *verified);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,10 @@ STL_AUTH_BAD_AUTH_MASTER = 4
 STL_AUTH_NO_ACCOUNT = 5
 STL_AUTH_UNDECIDED = 6
 
+# verified-ID cache (stl_sigcache_*)
+STL_SIGCACHE_MAX_SETS_LOG2 = 24
+STL_SIGCACHE_WAYS = 4
+
 # Every entry point include/stl.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U8P = ctypes.c_void_p
@@ -167,6 +171,15 @@ SYMBOLS = [
     ("stl_acctdir_tx_blob_authority_device", ctypes.c_int,
      [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),
     ("stl_acctdir_tx_blob_authority", ctypes.c_int, [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P]),
+    ("stl_sigcache_create", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, _P]),
+    ("stl_sigcache_destroy", None, [_P]),
+    ("stl_sigcache_get_info", ctypes.c_int, [_P, _P]),
+    ("stl_sigcache_clear", ctypes.c_int, [_P, _P]),
+    ("stl_sigcache_lookup_device", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _P, _P]),
+    ("stl_sigcache_signed_blob_verify_batch_device", ctypes.c_int,
+     [_P, _U8P, _P, _P, ctypes.c_size_t, _P, _U8P, _U8P, ctypes.c_uint32, _P, _P, _P]),
+    ("stl_sigcache_signed_blob_verify_batch", ctypes.c_int,
+     [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, ctypes.c_uint32, _P, _P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -11,6 +11,8 @@
                                  function
   tests/native/libhostemu_acctdir.so  the account directory's hash, probe,
                                  two-step insert and decision function
+  tests/native/libhostemu_sigcache.so  the verified-ID cache's hash, probe
+                                 and insert
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -26,13 +28,15 @@ CSRC = os.path.join(ROOT, "stellard_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_api.cpp",
+PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
+                "stl_api.cpp",
                 "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
                                "stl_comb.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h",
                                "stl_hash160.h", "stl_signer_core.h", "stl_signer.h",
                                "stl_acctdir_core.h", "stl_acctdir.h",
+                               "stl_sigcache_core.h", "stl_sigcache.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
 
@@ -64,7 +68,7 @@ def _run(cmd, cwd=ROOT):
 # launcher declarations, so a host-side change does not recompile the kernels
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
 HOST_DEPS = ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
-             "stl_acctdir.h", "stl_acctdir_core.h", os.path.join("..", "..", "include", "stl.h")]
+             "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -157,6 +161,15 @@ def build_hostemu_acctdir(force=False):
     return out
 
 
+def build_hostemu_sigcache(force=False):
+    out = os.path.join(ROOT, "tests", "native", "libhostemu_sigcache.so")
+    src = os.path.join(ROOT, "tests", "native", "hostemu_sigcache.cpp")
+    deps = [src, os.path.join(CSRC, "stl_sigcache_core.h")]
+    if force or _stale(out, deps):
+        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
+    return out
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -175,11 +188,11 @@ def main(argv=None):
     # the product and the host harness are independent single-threaded
     # compiles of the same device code: run them side by side
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=7) as ex:
+    with ThreadPoolExecutor(max_workers=8) as ex:
         jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force),
                 ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force),
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
-                ex.submit(build_hostemu_acctdir, force)]
+                ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force)]
         for j in jobs:
             j.result()
     build_oracle()

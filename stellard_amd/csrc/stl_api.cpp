@@ -46,6 +46,8 @@
 #include "stl_acctdir.h"
 #include "stl_acctdir_core.h"
 #include "stl_signer.h"
+#include "stl_sigcache.h"
+#include "stl_sigcache_core.h"
 
 namespace {
 
@@ -1478,6 +1480,7 @@ void keysets_release_all() {
 }
 
 void acctdirs_release_all();  // the account directories, further down
+void sigcaches_release_all();  // the verified-ID caches, further down
 
 int check_keyset_flags(uint32_t flags) {
   return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_DEBUG_RAW_PREDICATE)) ? STL_EINVAL : STL_OK;
@@ -1589,6 +1592,7 @@ void stl_shutdown(void) {
   stl_comm_destroy();
   keysets_release_all();
   acctdirs_release_all();
+  sigcaches_release_all();
   DeviceGuard guard;
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto& d : g_devs) {
@@ -3050,6 +3054,292 @@ int stl_tx_blob_signer_batch(const uint8_t* blobs, const uint64_t* offset, const
   std::memcpy(signer_id, host.data(), idb);
   if (account) std::memcpy(account, host.data() + idb, idb);
   std::memcpy(authority, host.data() + 2 * idb, n);
+  return span.finish(STL_OK);
+}
+
+}  // extern "C"
+
+// ---- verified-ID cache: rows already accepted skip the verify (stl_sigcache.hip) ----
+// One cache: on one device the lines (stl_sigcache_core.h), and what it is
+// bound to -- the blob kind and the accept predicate of the rows it may hold.
+struct stl_sigcache {
+  int ordinal = -1;
+  uint32_t sets_log2 = 0, kind = 0, predicate = 0;
+  uint64_t seed = 0;
+  DevBuf lines;
+  stl::SigCacheDev dev() const {
+    return stl::SigCacheDev{static_cast<uint32_t*>(lines.p), (1u << sets_log2) - 1u, seed};
+  }
+};
+
+namespace {
+// The live caches; g_sc_mu as g_ks_mu for the keysets: held while a call looks
+// its handle up and enqueues kernels that touch the lines, and while a cache
+// is destroyed.  Lock order: g_sc_mu before a device's mu / a context's mu.
+std::mutex g_sc_mu;
+std::set<const stl_sigcache*> g_sigcaches;
+
+void sigcache_free_locked(stl_sigcache* c) {
+  g_sigcaches.erase(c);
+  DeviceGuard guard;
+  if (hipSetDevice(c->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
+  c->lines.release();
+  delete c;
+}
+
+void sigcaches_release_all() {
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  while (!g_sigcaches.empty()) sigcache_free_locked(const_cast<stl_sigcache*>(*g_sigcaches.begin()));
+}
+
+// The live cache of a handle on the calling thread's device (g_sc_mu held),
+// by acctdir_for_call's rule; without a device STL_ENODEV comes first.
+int sigcache_for_call(const stl_sigcache* c, Device** d) {
+  STL_RC(device_for_call(d));
+  if (!c || !g_sigcaches.count(c)) return STL_EINVAL;
+  return (*d)->ordinal == c->ordinal ? STL_OK : STL_EINVAL;
+}
+
+// The cached blob verify of n rows on stream s (kl: g_sc_mu, held; c live on
+// d).  The blob pass into the lease's buffers, the probe with the miss list,
+// both counts copied to the lease's host-mapped words behind an event; then
+// the one wait -- for that event, with g_sc_mu released -- and the rows that
+// missed go through run_verify, compacted, their bits ORed into the bitmap
+// the probe wrote.  The insert comes last, under g_sc_mu again (the handle
+// looked up anew: the lines must still be there; `hold`: the host form, which
+// also holds its device's mutex, keeps g_sc_mu throughout instead, by the
+// lock order), and only after every
+// earlier step was enqueued without an error: the compact bitmap it reads is
+// then written in full by this call's verify, so a failed call leaves inserts
+// out but never adds an ID whose verify did not run.
+int sigcache_verify(std::unique_lock<std::mutex>& kl, Device& d, const stl_sigcache* c, ByKeyLease& use,
+                    const uint8_t* d_blobs, const uint64_t* d_offset, const uint32_t* d_len, size_t n,
+                    uint64_t* d_words, uint8_t* d_status, uint8_t* d_id, uint32_t flags, hipStream_t s,
+                    size_t* hits, size_t* verified, bool hold = false) {
+  ByKeyBufs& b = use.b;
+  const stl::SigCacheDev cd = c->dev();
+  const uint32_t kind = c->kind;
+  // signing hashes, signatures, keys; then the IDs when the caller takes none
+  STL_RC(b.blob.ensure(n * (d_id ? 128 : 160)));
+  uint8_t* msg = static_cast<uint8_t*>(b.blob.p);
+  uint8_t* sig = msg + 32 * n;
+  uint8_t* pk = msg + 96 * n;
+  uint8_t* ids = d_id ? d_id : msg + 128 * n;
+  {
+    // the pass of stl_signed_blob_prepare_device; the context's queue under
+    // its mutex until the kernel using it is enqueued
+    std::lock_guard<std::mutex> cl(use.c->mu);
+    uint32_t* ctr = nullptr;
+    STL_RC(ctx_queue(*use.c, n, &ctr, true));
+    STL_TRY(stl::launch_tx_blob(d_blobs, d_offset, d_len, (uint32_t)n, msg, sig, pk, ids, d_status, ctr,
+                                hash_grid(d), s, kind));
+  }
+  STL_RC(b.idx.ensure(256 + align256(n * 4)));
+  if (!b.count) {
+    void* p = nullptr;
+    STL_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    b.count = static_cast<uint32_t*>(p);
+  }
+  if (!b.counted) STL_TRY(hipEventCreateWithFlags(&b.counted, hipEventDisableTiming));
+  uint8_t* base = static_cast<uint8_t*>(b.idx.p);
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(base);  // [0] misses, [1] hits
+  uint32_t* miss_rows = reinterpret_cast<uint32_t*>(base + 256);
+  STL_TRY(hipMemsetAsync(cnt, 0, 8, s));
+  STL_TRY(stl::launch_sigcache_probe(cd, ids, d_status, (uint32_t)n, d_words, miss_rows, cnt, dev_counters(d), s));
+  STL_TRY(hipMemcpyAsync(b.count, cnt, 8, hipMemcpyDeviceToHost, s));
+  STL_TRY(hipEventRecord(b.counted, s));
+  if (!hold) kl.unlock();
+  // the call's one host wait: the per-signature kernels are sized by the miss count
+  STL_TRY(hipEventSynchronize(b.counted));
+  const size_t m = __atomic_load_n(&b.count[0], __ATOMIC_ACQUIRE);
+  const size_t h = __atomic_load_n(&b.count[1], __ATOMIC_ACQUIRE);
+  if (m + h > n) return STL_EHIP;
+  if (hits) *hits = h;
+  if (verified) *verified = m;
+  if (m == 0) return STL_OK;  // every decidable row a hit: no per-signature kernel
+  const size_t csig = 0, cmsg = align256(m * 64), cpk = cmsg + align256(m * 32), cwords = cpk + align256(m * 32);
+  STL_RC(b.rows.ensure(cwords + (m + 63) / 64 * 8));
+  uint8_t* r = static_cast<uint8_t*>(b.rows.p);
+  STL_TRY(stl::launch_keyset_gather_rows(miss_rows, (uint32_t)m, sig, msg, pk, r + csig, r + cmsg, r + cpk, s));
+  // the mode the flags give and the stream's automatic dedup, sampled on the
+  // compact keys, as the by-key call runs its misses
+  uint32_t mode = stl::kernel_mode(flags);
+  uint32_t* flag_dev = nullptr;
+  STL_RC(auto_dedup_device(*use.c, flags, &mode, &flag_dev));
+  STL_RC(run_verify(d, s, r + csig, r + cmsg, r + cpk, m, reinterpret_cast<uint64_t*>(r + cwords), mode, false,
+                    g_tune_streams.load()));
+  if (flag_dev) STL_TRY(stl::launch_key_sample(r + cpk, (uint32_t)m, flag_dev, s));
+  STL_TRY(stl::launch_keyset_scatter_bits(miss_rows, (uint32_t)m, reinterpret_cast<const uint64_t*>(r + cwords),
+                                          d_words, s));
+  if (!hold) kl.lock();
+  if (!g_sigcaches.count(c)) return STL_OK;  // destroyed during the wait: the outputs stand, nothing to insert into
+  STL_TRY(stl::launch_sigcache_insert(cd, miss_rows, (uint32_t)m, reinterpret_cast<const uint64_t*>(r + cwords), ids,
+                                      s));
+  return STL_OK;
+}
+
+int check_sigcache_rows(const void* blobs, const void* offset, const void* len, size_t n, const void* bitmap,
+                        const void* status, const void* id, uint32_t flags) {
+  if (n > 0xffffffc0ull || (n && (!blobs || !offset || !len || !bitmap || !status))) return STL_EINVAL;
+  if (((uintptr_t)id & 15u) != 0) return STL_EINVAL;
+  return check_flags(flags);
+}
+}  // namespace
+
+extern "C" {
+
+int stl_sigcache_create(uint32_t sets_log2, uint32_t kind, uint32_t flags, uint64_t seed, stl_sigcache** out) {
+  if (out) *out = nullptr;
+  if (!out || sets_log2 > STL_SIGCACHE_MAX_SETS_LOG2) return STL_EINVAL;
+  if (kind != STL_BLOB_TRANSACTION && kind != STL_BLOB_VALIDATION) return STL_EINVAL;
+  STL_RC(check_keyset_flags(flags));  // the predicate bits; no execution flag belongs to a cache
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  while (seed == 0) {
+    std::random_device rd;
+    seed = ((uint64_t)rd() << 32) ^ rd();
+  }
+  std::unique_ptr<stl_sigcache> c(new stl_sigcache());
+  c->ordinal = d->ordinal;
+  c->sets_log2 = sets_log2;
+  c->kind = kind;
+  c->predicate = stl::sigcache_predicate(flags);
+  c->seed = seed;
+  const size_t bytes = stl::sigcache_bytes(sets_log2);
+  DeviceGuard guard;
+  auto go = [&]() -> int {
+    std::lock_guard<std::mutex> lk(d->mu);
+    STL_TRY(hipSetDevice(d->ordinal));
+    STL_RC(c->lines.ensure(bytes));
+    STL_TRY(hipMemsetAsync(c->lines.p, 0, bytes, d->stream));
+    STL_TRY(hipStreamSynchronize(d->stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    c->lines.release();
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  g_sigcaches.insert(c.get());
+  *out = c.release();
+  return STL_OK;
+}
+
+void stl_sigcache_destroy(stl_sigcache* c) {
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  if (c && g_sigcaches.count(c)) sigcache_free_locked(c);
+}
+
+int stl_sigcache_get_info(const stl_sigcache* c, stl_sigcache_info* out) {
+  if (!out || out->struct_size != sizeof(stl_sigcache_info)) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  if (!c || !g_sigcaches.count(c)) return STL_EINVAL;
+  out->sets_log2 = c->sets_log2;
+  out->ways = STL_SIGCACHE_WAYS;
+  out->kind = c->kind;
+  out->predicate = c->predicate;
+  out->device = c->ordinal;
+  out->bytes = stl::sigcache_bytes(c->sets_log2);
+  out->seed = c->seed;
+  return STL_OK;
+}
+
+int stl_sigcache_clear(stl_sigcache* c, void* stream) {
+  if (!c) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  Device* d = nullptr;
+  STL_RC(sigcache_for_call(c, &d));
+  STL_TRY(hipMemsetAsync(c->lines.p, 0, stl::sigcache_bytes(c->sets_log2), static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_sigcache_lookup_device(stl_sigcache* c, const uint8_t* d_id, size_t n, uint64_t* d_hit_words, void* stream) {
+  if (!c) return STL_EINVAL;
+  if (n > 0xffffffc0ull || (n && (!d_id || !d_hit_words)) || ((uintptr_t)d_id & 15u) != 0) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_sc_mu);
+  Device* d = nullptr;
+  STL_RC(sigcache_for_call(c, &d));
+  if (n == 0) return STL_OK;
+  STL_TRY(stl::launch_sigcache_lookup(c->dev(), d_id, (uint32_t)n, d_hit_words, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_sigcache_signed_blob_verify_batch_device(stl_sigcache* c, const uint8_t* d_blobs, const uint64_t* d_offset,
+                                                 const uint32_t* d_len, size_t n, uint64_t* d_bitmap_words,
+                                                 uint8_t* d_status, uint8_t* d_id, uint32_t flags, void* stream,
+                                                 size_t* hits, size_t* verified) {
+  if (hits) *hits = 0;
+  if (verified) *verified = 0;
+  if (!c) return STL_EINVAL;
+  STL_RC(check_sigcache_rows(d_blobs, d_offset, d_len, n, d_bitmap_words, d_status, d_id, flags));
+  std::unique_lock<std::mutex> kl(g_sc_mu);
+  Device* d = nullptr;
+  STL_RC(sigcache_for_call(c, &d));
+  if (stl::sigcache_predicate(flags) != c->predicate) return STL_EINVAL;
+  if (n == 0) return STL_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ByKeyLease use(stream_ctx(*d, s), s);
+  return sigcache_verify(kl, *d, c, use, d_blobs, d_offset, d_len, n, d_bitmap_words, d_status, d_id, flags, s, hits,
+                         verified);
+}
+
+int stl_sigcache_signed_blob_verify_batch(stl_sigcache* c, const uint8_t* blobs, const uint64_t* offset,
+                                          const uint32_t* len, size_t n, uint8_t* accept_bitmap, uint8_t* status,
+                                          uint8_t* id, uint32_t flags, size_t* hits, size_t* verified) {
+  if (hits) *hits = 0;
+  if (verified) *verified = 0;
+  if (!c) return STL_EINVAL;
+  STL_RC(check_sigcache_rows(blobs, offset, len, n, accept_bitmap, status, nullptr, flags));
+  std::unique_lock<std::mutex> kl(g_sc_mu);
+  Device* dp = nullptr;
+  STL_RC(sigcache_for_call(c, &dp));
+  if (stl::sigcache_predicate(flags) != c->predicate) return STL_EINVAL;
+  if (n == 0) return STL_OK;
+  Device& d = *dp;
+  CallSpan span{"stl_sigcache_signed_blob_verify_batch", n};
+  DeviceGuard guard;
+  std::lock_guard<std::mutex> dl(d.mu);
+  std::vector<uint64_t> roff, row_end;
+  uint64_t base = 0, bytes = 0;
+  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
+  const size_t words = (n + 63) / 64;
+  std::vector<uint64_t> host_words(words);
+  std::vector<uint8_t> host(n + (id ? 32 * n : 0));  // status, then the IDs
+  auto go = [&]() -> int {
+    STL_TRY(hipSetDevice(d.ordinal));
+    STL_RC(d.pre.ensure(bytes + 16));
+    STL_RC(d.off.ensure(n * 8));
+    STL_RC(d.len.ensure(n * 4));
+    STL_RC(d.bitmap.ensure(words * 8));
+    STL_RC(d.status.ensure(n));
+    if (id) STL_RC(d.txid.ensure(n * 32));
+    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
+    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
+    if (id) STL_TRY(hipMemsetAsync(d.txid.p, 0, n * 32, d.stream));  // a malformed row's ID is not written
+    {
+      ByKeyLease use(stream_ctx(d, d.stream), d.stream);
+      STL_RC(sigcache_verify(kl, d, c, use, static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
+                             static_cast<const uint32_t*>(d.len.p), n, static_cast<uint64_t*>(d.bitmap.p),
+                             static_cast<uint8_t*>(d.status.p), id ? static_cast<uint8_t*>(d.txid.p) : nullptr, flags,
+                             d.stream, hits, verified, true));
+    }
+    STL_TRY(hipMemcpyAsync(host_words.data(), d.bitmap.p, words * 8, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipMemcpyAsync(host.data(), d.status.p, n, hipMemcpyDeviceToHost, d.stream));
+    if (id) STL_TRY(hipMemcpyAsync(host.data() + n, d.txid.p, 32 * n, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {  // nothing may still read the caller's rows or write the host buffers
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  std::memcpy(accept_bitmap, host_words.data(), (n + 7) / 8);
+  std::memcpy(status, host.data(), n);
+  if (id) std::memcpy(id, host.data() + n, 32 * n);
   return span.finish(STL_OK);
 }
 

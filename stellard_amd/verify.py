@@ -632,6 +632,142 @@ class AccountDirectory:
         return (signer[:n] if signer_ids else None), (account[:n] if accounts else None), authority[:n]
 
 
+# ---- verified-ID cache (stl_sigcache_*) ----
+
+SIGCACHE_MAX_SETS_LOG2, SIGCACHE_WAYS = N.STL_SIGCACHE_MAX_SETS_LOG2, N.STL_SIGCACHE_WAYS
+
+
+class SigCacheInfo(ctypes.Structure):
+    """stl_sigcache_info (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("sets_log2", ctypes.c_uint32), ("ways", ctypes.c_uint32),
+                ("kind", ctypes.c_uint32), ("predicate", ctypes.c_uint32), ("device", ctypes.c_int32),
+                ("bytes", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
+
+
+class SigCache:
+    """A device-resident cache of the IDs of signed objects the verify has
+    accepted (stl_sigcache_create), bound to one blob kind and one accept
+    predicate (``policy``: the policy bit, N.STL_DEBUG_RAW_PREDICATE).  A row
+    whose ID is found skips the Ed25519 verify; the outputs are those of
+    signed_blob_verify_batch_device on every input.
+
+        with SigCache(20) as c:
+            out = c.signed_blob_verify_batch_device(blobs, offsets, lengths)   # ingest
+            out = c.signed_blob_verify_batch_device(blobs, offsets, lengths)   # ledger close: all hits
+    """
+
+    def __init__(self, sets_log2, kind=BLOB_TRANSACTION, policy=POLICY_SODIUM_1_0_18, seed=0):
+        h = ctypes.c_void_p()
+        N.check(N.load().stl_sigcache_create(int(sets_log2), int(kind), int(policy), int(seed), ctypes.byref(h)),
+                "stl_sigcache_create")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            N.load().stl_sigcache_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        i = SigCacheInfo(struct_size=ctypes.sizeof(SigCacheInfo))
+        N.check(N.load().stl_sigcache_get_info(self._h, ctypes.byref(i)), "stl_sigcache_get_info")
+        return {k: getattr(i, k) for k, _ in SigCacheInfo._fields_ if k != "struct_size"}
+
+    def clear(self, stream=None):
+        """Empties the cache: a memset enqueued on ``stream``."""
+        N.check(N.load().stl_sigcache_clear(self._h, _stream_ptr(stream)), "stl_sigcache_clear")
+
+    def lookup_device(self, ids, out_words=None, stream=None):
+        """ids (n, 32) uint8 CUDA tensor -> int64[ceil(n/64)] bitmap words, bit
+        i = ID i is present (async on ``stream``)."""
+        import torch
+        if ids.dtype != torch.uint8:
+            raise ValueError("ids must be torch.uint8")
+        if ids.dim() != 2 or ids.shape[1] != 32:
+            raise ValueError("ids must be (n, 32) bytes")
+        n = ids.shape[0]
+        if out_words is None:
+            out_words = torch.empty((n + 63) // 64, dtype=torch.int64, device=ids.device)
+        if out_words.dtype != torch.int64 or out_words.numel() < (n + 63) // 64:
+            raise ValueError("out_words must be int64, one word per 64 rows")
+        for t in (ids, out_words):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        N.check(N.load().stl_sigcache_lookup_device(self._h, ctypes.c_void_p(ids.data_ptr()), n,
+                                                    ctypes.c_void_p(out_words.data_ptr()), _stream_ptr(stream)),
+                "stl_sigcache_lookup_device")
+        return out_words
+
+    def signed_blob_verify_batch_device(self, blobs, offsets, lengths, out_words=None, tx_ids=False, flags=None,
+                                        stream=None, out_status=None, out_ids=None):
+        """Serialized transactions / validations (the cache's kind) in HBM ->
+        dict of words, status, tx_id (as verify.signed_blob_verify_batch_device
+        writes them), hits and verified.  ``flags``: the cache's predicate by
+        default; execution flags (FULL_LENGTH, ...) may be ORed to it.  Waits
+        once on ``stream`` (for the probe)."""
+        import torch
+        n = offsets.shape[0]
+        dev = blobs.device
+        if out_words is None:
+            out_words = torch.empty(((n + 63) // 64,), dtype=torch.int64, device=dev)
+        status = torch.empty((n,), dtype=torch.uint8, device=dev) if out_status is None else out_status
+        tx_id = out_ids if out_ids is not None else (torch.empty((n, 32), dtype=torch.uint8, device=dev)
+                                                     if tx_ids else None)
+        if status.dtype != torch.uint8 or (tx_id is not None and tx_id.dtype != torch.uint8):
+            raise ValueError("out_status / out_ids must be torch.uint8")
+        if tx_id is not None and tx_id.dim() > 1 and tx_id.shape[-1] != 32:
+            raise ValueError("out_ids must be (n, 32) bytes")
+        if status.numel() < n or (tx_id is not None and tx_id.numel() < 32 * n):
+            raise ValueError("status / id buffers smaller than the batch")
+        if out_words.dtype != torch.int64 or out_words.numel() < (n + 63) // 64:
+            raise ValueError("out_words must be int64, one word per 64 rows")
+        if blobs.dtype != torch.uint8:
+            raise ValueError("blobs must be torch.uint8")
+        _check_rows(blobs, offsets, lengths, out_words, status, tx_id)
+        if flags is None:
+            flags = self.info()["predicate"]
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        hits, verified = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        N.check(N.load().stl_sigcache_signed_blob_verify_batch_device(
+            self._h, p(blobs), p(offsets), p(lengths), n, p(out_words), p(status), p(tx_id), int(flags),
+            _stream_ptr(stream), ctypes.byref(hits), ctypes.byref(verified)),
+            "stl_sigcache_signed_blob_verify_batch_device")
+        return {"words": out_words, "status": status, "tx_id": tx_id, "hits": int(hits.value),
+                "verified": int(verified.value)}
+
+    def signed_blob_verify_batch(self, blobs, ids=False, flags=None):
+        """Host form: list of bytes -> (accept bool[n], status uint8[n], ids
+        (n, 32) or None, hits, verified)."""
+        n = len(blobs)
+        buf, offs, lens = _pack(blobs)
+        bitmap = np.zeros((n + 7) // 8 or 1, dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        idb = np.zeros((max(n, 1), 32), dtype=np.uint8) if ids else None
+        if flags is None:
+            flags = self.info()["predicate"]
+        hits, verified = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        N.check(N.load().stl_sigcache_signed_blob_verify_batch(
+            self._h, _buf(buf), _buf(offs), _buf(lens), n, _buf(bitmap), _buf(status), _buf(idb) if ids else None,
+            int(flags), ctypes.byref(hits), ctypes.byref(verified)), "stl_sigcache_signed_blob_verify_batch")
+        return (unpack_bitmap(bitmap, n), status[:n], idb[:n] if ids else None, int(hits.value),
+                int(verified.value))
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
