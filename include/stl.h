@@ -540,6 +540,26 @@ int stl_debug_key_cache_info(void **d_base, uint64_t *bytes, uint32_t *sets_log2
  * register}.  Two stamps around a timed region give its average shader clock
  * per XCD.  STL_EINVAL for a null d_out or nwg > 65,536. */
 int stl_debug_clock_stamp(uint64_t *d_out, uint32_t nwg, void *stream);
+/* Tests only: the field, scalar and group arithmetic under the verify kernels,
+ * one function at a time, as the device compiles it.  _ops runs op (an index
+ * into the table of stellard_amd/csrc/stl_selftest.h, which also documents the
+ * row formats) on n rows, one lane per row: row i is the STL_SELFTEST_IN_WORDS
+ * 32-bit words from d_in + STL_SELFTEST_IN_WORDS * i (raw limbs or scalar
+ * words, nothing reduced), its result the STL_SELFTEST_OUT_WORDS words at
+ * d_out + STL_SELFTEST_OUT_WORDS * i.  _group runs a lane-group formula of the
+ * small-batch kernels on nrows rows, row r on all G lanes of group r (G = 2 or
+ * 4); every lane writes its own record, so d_out receives nrows * G records,
+ * record G r + j from lane j of group r.  Nothing outside those records is
+ * written.  STL_EINVAL for an op outside the table, G other than 2 or 4, more
+ * than STL_SELFTEST_MAX_ROWS rows, or a null pointer with rows to run. */
+#define STL_SELFTEST_OPS 47
+#define STL_SELFTEST_GROUP_OPS 7
+#define STL_SELFTEST_IN_WORDS 72
+#define STL_SELFTEST_OUT_WORDS 40
+#define STL_SELFTEST_MAX_ROWS 1048576
+int stl_debug_selftest_ops_device(uint32_t op, const uint32_t *d_in, size_t n, uint32_t *d_out, void *stream);
+int stl_debug_selftest_group_device(uint32_t op, uint32_t G, const uint32_t *d_in, size_t nrows, uint32_t *d_out,
+                                    void *stream);
 
 /* Drops libstl's context of a caller stream on the current device -- its
  * verify workspace, hash queue, checkSign scratch and events -- without

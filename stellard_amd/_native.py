@@ -85,6 +85,13 @@ STL_AUTH_UNDECIDED = 6
 STL_SIGCACHE_MAX_SETS_LOG2 = 24
 STL_SIGCACHE_WAYS = 4
 
+# arithmetic self-test (stl_debug_selftest_*; row formats in csrc/stl_selftest.h)
+STL_SELFTEST_OPS = 47
+STL_SELFTEST_GROUP_OPS = 7
+STL_SELFTEST_IN_WORDS = 72
+STL_SELFTEST_OUT_WORDS = 40
+STL_SELFTEST_MAX_ROWS = 1048576
+
 # Every entry point include/stl.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U8P = ctypes.c_void_p
@@ -140,6 +147,9 @@ SYMBOLS = [
     ("stl_debug_key_cache_clear", ctypes.c_int, []),
     ("stl_debug_key_cache_info", ctypes.c_int, [_P, _P, _P, _P]),
     ("stl_debug_clock_stamp", ctypes.c_int, [_P, ctypes.c_uint32, _P]),
+    ("stl_debug_selftest_ops_device", ctypes.c_int, [ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P]),
+    ("stl_debug_selftest_group_device", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, _P]),
     ("stl_release_stream", ctypes.c_int, [_P]),
     ("stl_debug_sign_adversarial_device", ctypes.c_int,
      [_U8P, _U8P, _U8P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, _P]),

@@ -22,6 +22,7 @@ import os
 import shutil
 import subprocess
 import sys
+import threading
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stellard_amd", "csrc")
@@ -29,6 +30,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
+                "stl_selftest.hip",
                 "stl_api.cpp",
                 "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
@@ -37,6 +39,7 @@ PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe2551
                                "stl_hash160.h", "stl_signer_core.h", "stl_signer.h",
                                "stl_acctdir_core.h", "stl_acctdir.h",
                                "stl_sigcache_core.h", "stl_sigcache.h",
+                               "stl_group.h", "stl_selftest.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
 
@@ -122,52 +125,58 @@ def build_hostemu_keyset(force=False):
     return out
 
 
+# The quick host harnesses (a few seconds each): name -> (source, csrc deps).
+SMALL_HARNESSES = {
+    "keyset_map": ("hostemu_keyset_map.cpp", ("stl_keyset_map.h",)),
+    "keycache": ("hostemu_keycache.cpp", ("stl_keycache.h", "stl_fe25519.h", "stl_ge25519.h", "stl_kernels.h")),
+    "signer": ("hostemu_signer.cpp", ("stl_hash160.h", "stl_signer_core.h", "stl_txblob.h", "stl_sha512.h",
+                                      "stl_fe25519.h")),
+    "acctdir": ("hostemu_acctdir.cpp", ("stl_acctdir_core.h", "stl_hash160.h", "stl_signer_core.h", "stl_txblob.h",
+                                        "stl_sha512.h", "stl_fe25519.h")),
+    "sigcache": ("hostemu_sigcache.cpp", ("stl_sigcache_core.h",)),
+}
+_small_lock = threading.Lock()
+
+
+def _small_out(name):
+    return os.path.join(ROOT, "tests", "native", f"libhostemu_{name}.so")
+
+
+def _build_small(name, force=False):
+    """Builds one quick harness if stale, then any other quick harness whose
+    library is absent: the test modules build theirs on load, each through
+    its own entry below, except tests/sigcache_py.py as first committed, which
+    only opens libhostemu_sigcache.so -- a tree whose tests/native lost its
+    libraries after build() is whole again once any of them has loaded."""
+    with _small_lock:
+        for n in [name] + [m for m in SMALL_HARNESSES if m != name]:
+            src, hdrs = SMALL_HARNESSES[n]
+            src = os.path.join(ROOT, "tests", "native", src)
+            out = _small_out(n)
+            deps = [src] + [os.path.join(CSRC, h) for h in hdrs]
+            if n == name and (force or _stale(out, deps)) or n != name and not os.path.exists(out):
+                _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
+    return _small_out(name)
+
+
 def build_hostemu_keyset_map(force=False):
-    out = os.path.join(ROOT, "tests", "native", "libhostemu_keyset_map.so")
-    src = os.path.join(ROOT, "tests", "native", "hostemu_keyset_map.cpp")
-    deps = [src, os.path.join(CSRC, "stl_keyset_map.h")]
-    if force or _stale(out, deps):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return out
+    return _build_small("keyset_map", force)
 
 
 def build_hostemu_keycache(force=False):
-    out = os.path.join(ROOT, "tests", "native", "libhostemu_keycache.so")
-    src = os.path.join(ROOT, "tests", "native", "hostemu_keycache.cpp")
-    deps = [src] + [os.path.join(CSRC, d) for d in ("stl_keycache.h", "stl_fe25519.h", "stl_ge25519.h",
-                                                    "stl_kernels.h")]
-    if force or _stale(out, deps):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return out
+    return _build_small("keycache", force)
 
 
 def build_hostemu_signer(force=False):
-    out = os.path.join(ROOT, "tests", "native", "libhostemu_signer.so")
-    src = os.path.join(ROOT, "tests", "native", "hostemu_signer.cpp")
-    deps = [src] + [os.path.join(CSRC, d) for d in ("stl_hash160.h", "stl_signer_core.h", "stl_txblob.h",
-                                                    "stl_sha512.h", "stl_fe25519.h")]
-    if force or _stale(out, deps):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return out
+    return _build_small("signer", force)
 
 
 def build_hostemu_acctdir(force=False):
-    out = os.path.join(ROOT, "tests", "native", "libhostemu_acctdir.so")
-    src = os.path.join(ROOT, "tests", "native", "hostemu_acctdir.cpp")
-    deps = [src] + [os.path.join(CSRC, d) for d in ("stl_acctdir_core.h", "stl_hash160.h", "stl_signer_core.h",
-                                                    "stl_txblob.h", "stl_sha512.h", "stl_fe25519.h")]
-    if force or _stale(out, deps):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return out
+    return _build_small("acctdir", force)
 
 
 def build_hostemu_sigcache(force=False):
-    out = os.path.join(ROOT, "tests", "native", "libhostemu_sigcache.so")
-    src = os.path.join(ROOT, "tests", "native", "hostemu_sigcache.cpp")
-    deps = [src, os.path.join(CSRC, "stl_sigcache_core.h")]
-    if force or _stale(out, deps):
-        _run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return out
+    return _build_small("sigcache", force)
 
 
 def build_oracle():

@@ -2281,6 +2281,27 @@ int stl_debug_clock_stamp(uint64_t* d_out, uint32_t nwg, void* stream) {
   return STL_OK;
 }
 
+int stl_debug_selftest_ops_device(uint32_t op, const uint32_t* d_in, size_t n, uint32_t* d_out, void* stream) {
+  if (op >= STL_SELFTEST_OPS || n > STL_SELFTEST_MAX_ROWS) return STL_EINVAL;
+  if (n == 0) return STL_OK;
+  if (!d_in || !d_out) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  STL_TRY(stl::launch_selftest_ops(op, d_in, (uint32_t)n, d_out, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_debug_selftest_group_device(uint32_t op, uint32_t G, const uint32_t* d_in, size_t nrows, uint32_t* d_out,
+                                    void* stream) {
+  if (op >= STL_SELFTEST_GROUP_OPS || (G != 2 && G != 4) || nrows > STL_SELFTEST_MAX_ROWS) return STL_EINVAL;
+  if (nrows == 0) return STL_OK;
+  if (!d_in || !d_out) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  STL_TRY(stl::launch_selftest_group(op, G, d_in, (uint32_t)nrows, d_out, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
 int stl_debug_verify_k_device(const uint8_t* d_sig, const uint8_t* d_k, const uint8_t* d_pk, size_t n,
                               uint64_t* d_bitmap_words, uint32_t flags, void* stream) {
   if (n == 0) return STL_OK;

@@ -7,16 +7,26 @@
 // 1.3x faster than the saturated 8x32 schedule (2.47e11 vs 1.91e11 fe_mul/s
 // per GPU), and additions need no carry chain at all.
 //
-// Limb-bound discipline ("alpha" = max limb / 2^29), checked by the
-// STL_FE_BOUNDS build of tests/native:
+// Limb-bound discipline ("alpha" = max limb / 2^29).  The preconditions are
+// counted by the hooks below in the host build (tests/native/hostemu.cpp);
+// the output bounds and the results at the edge of the preconditions are held
+// by tests/test_arith_ops_host.py, op by op against Python integers:
 //   * fe_mul / fe_sq output       alpha <= 1 + 2^-12
-//   * fe_carry / fe_sub / fe_neg  alpha <= 1 + 2^-16       (normalised)
+//   * fe_carry / fe_sub           alpha <= 1 + 2^-15       (normalised)
+//     limb 0 receives (limb 8 >> 29) * 1216, and a 32-bit limb 8 carries up
+//     to 7: limb 0 <= 2^29 - 1 + 8512, limbs 1..8 <= 2^29 + 6.  While limb 8
+//     before the pass is below 7 * 2^29 -- fe_sub with limb 8 of a below
+//     3 * 2^29, fe_neg, fe_carry of a sum [<= 6] -- the carry is at most
+//     6 * 1216 and alpha <= 1 + 2^-16; every call site of the group formulas
+//     (stl_ge25519.h: a is [1] or [2]) is in that case.
+//   * fe_neg                      alpha <= 1 + 2^-16
 //   * fe_add                      alpha = alpha_a + alpha_b (no carry)
 //   * fe_mul(a, b) requires  alpha_a * alpha_b <= 7  (each 64-bit column sum
 //     of 9 products then stays below 2^64); fe_sq requires alpha^2 <= 7.
 //   * fe_sub(a, b) requires alpha_a <= 3.9 and alpha_b <= 3.9.
-// Values are only weakly reduced (any representative < 2^262); fe_tobytes /
-// fe_iszero / fe_isnegative fully reduce mod p.
+// Values are only weakly reduced (any representative < 2^262 with limbs
+// <= 2^32 - 8: the first carry pass of fe_tobytes adds up to 7 to a limb);
+// fe_tobytes / fe_iszero / fe_isnegative fully reduce mod p.
 //
 // Same code compiles for the host (tests/native harness) and the device; it
 // is one implementation, not a fallback.

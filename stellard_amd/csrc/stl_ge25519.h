@@ -2,7 +2,15 @@
 // extended coordinates), in the representations ref10 uses:
 //   p2 (X:Y:Z), p3 (X:Y:Z:T), p1p1 ((X:Z),(Y:T)), cached (Y+X, Y-X, Z, 2dT),
 //   niels (y+x, y-x, 2dxy) for affine table points.
-// Limb bounds (see stl_fe25519.h) are annotated as [alpha].
+// Limb bounds (see stl_fe25519.h) are annotated as [alpha], rounded: with
+// e = 2^-12, [1] is a product (<= 1 + e) or an fe_sub / fe_carry result
+// (<= 1 + 2^-15 by the header's general bound, <= 1 + 2^-16 here, where the
+// minuend is never above [2]); [2] = 2 (1 + e), [3] = 3 + e and the lazy
+// [4] = 4 + e come from adding [1]s or 2 Z1 / 3 Z1.  The largest products of
+// the formulas below are then [2] * [3] = 6.003 and [4] * [1] = 4.002, well
+// inside fe_mul's alpha_a * alpha_b <= 7; no annotation depends on whether
+// an fe_sub result is 1 + 2^-16 or 1 + 2^-15.  tests/test_arith_ops_host.py
+// checks each formula's output limbs against these bounds.
 #pragma once
 #include "stl_fe25519.h"
 

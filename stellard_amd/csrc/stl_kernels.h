@@ -240,6 +240,13 @@ hipError_t launch_key_sample(const uint8_t* pk, uint32_t n, uint32_t* flag, hipS
 hipError_t launch_wide_table(uint4* out, hipStream_t stream);
 // nwg one-wave workgroups, each {memtime, memrealtime, XCC_ID, HW_ID} (4 u64)
 hipError_t launch_clock_stamp(unsigned long long* out, uint32_t nwg, hipStream_t stream);
+// Arithmetic self-test (stl_selftest.hip; row formats in stl_selftest.h): op
+// on n rows, one lane per row; and a lane-group op on nrows rows, one group
+// of G lanes per row, every lane writing its own record (nrows * G records).
+// hipErrorInvalidValue for an unknown op or G not 2 or 4.
+hipError_t launch_selftest_ops(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t stream);
+hipError_t launch_selftest_group(uint32_t op, uint32_t G, const uint32_t* in, uint32_t nrows, uint32_t* out,
+                                 hipStream_t stream);
 // cls / param (nullable, test data only): per-row adversarial class and its
 // parameter (stl_kernels.hip adversarial_row); msg_out receives the messages.
 hipError_t launch_sign(const uint8_t* seed, const uint8_t* msg, uint32_t n, uint8_t* pk, uint8_t* sig, uint4* ws,

@@ -1227,6 +1227,35 @@ def clock_stamp(nwg=256, stream=None):
     return out
 
 
+def selftest_ops_device(op, rows, out=None, stream=None):
+    """stl_debug_selftest_ops_device (tests only): ``op`` on ``rows``, an
+    (n, STL_SELFTEST_IN_WORDS) int32 CUDA tensor of raw words; returns the
+    (n, STL_SELFTEST_OUT_WORDS) int32 results (``out``, if given, receives
+    them at its start)."""
+    import torch
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty((n, N.STL_SELFTEST_OUT_WORDS), dtype=torch.int32, device=rows.device)
+    N.check(N.load().stl_debug_selftest_ops_device(op, ctypes.c_void_p(rows.data_ptr()), n,
+                                                   ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+            "stl_debug_selftest_ops_device")
+    return out
+
+
+def selftest_group_device(op, group, rows, out=None, stream=None):
+    """stl_debug_selftest_group_device (tests only): lane-group formula
+    ``op`` with ``group`` = 2 or 4 lanes per row; returns (n * group,
+    STL_SELFTEST_OUT_WORDS) int32 records, one per lane."""
+    import torch
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty((n * group, N.STL_SELFTEST_OUT_WORDS), dtype=torch.int32, device=rows.device)
+    N.check(N.load().stl_debug_selftest_group_device(op, group, ctypes.c_void_p(rows.data_ptr()), n,
+                                                     ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+            "stl_debug_selftest_group_device")
+    return out
+
+
 def clock_ghz(start, end):
     """Average shader clock (GHz) between two clock_stamp results (numpy or
     torch (nwg, 4)).  Each CU keeps its own cycle counter (tools/clock_probe.py:

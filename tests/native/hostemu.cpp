@@ -12,6 +12,10 @@
 
 static std::atomic<uint64_t> g_bound_viol{0};
 static std::atomic<uint64_t> g_bound_checks{0};
+// where this thread's hooks count: the process-wide total the verify entries
+// report, or hostemu_selftest_ops' own counter while it runs (its arming rows
+// violate on purpose and must not show in the verify paths' totals)
+static thread_local std::atomic<uint64_t>* t_bound_viol = &g_bound_viol;
 
 #define STL_BOUND_MUL(a, b) hostemu_check_mul((a), (b))
 #define STL_BOUND_SUB(a, b) hostemu_check_sub((a), (b))
@@ -28,6 +32,7 @@ static void hostemu_check_subk(const stl::fe& a, const stl::fe& b, int k);
 // verify path and the blob pass are compiled -- the sanitized build of every
 // table-layout variant and the signer took over twelve minutes
 #ifndef HOSTEMU_SANITIZE_SUBSET
+#include "../../stellard_amd/csrc/stl_selftest.h"
 #include "../../stellard_amd/csrc/stl_sign.h"
 #endif
 
@@ -38,7 +43,7 @@ static double alpha(const stl::fe& a) {
 }
 static void hostemu_check_mul(const stl::fe& a, const stl::fe& b) {
   g_bound_checks++;
-  if (alpha(a) * alpha(b) > 7.0) g_bound_viol++;
+  if (alpha(a) * alpha(b) > 7.0) (*t_bound_viol)++;
 }
 // fe_sub_nc<K>: no limb of b above K*Z1's, and a + K*Z1 within 32 bits
 static void hostemu_check_subk(const stl::fe& a, const stl::fe& b, int k) {
@@ -46,11 +51,11 @@ static void hostemu_check_subk(const stl::fe& a, const stl::fe& b, int k) {
   bool bad = b.v[0] > (uint64_t)k * 0x1ffffb40u;
   for (int i = 1; i < 9; ++i) bad = bad || b.v[i] > (uint64_t)k * 0x1fffffffu;
   for (int i = 0; i < 9; ++i) bad = bad || (uint64_t)a.v[i] + (uint64_t)k * 0x1fffffffu > 0xffffffffull;
-  if (bad) g_bound_viol++;
+  if (bad) (*t_bound_viol)++;
 }
 static void hostemu_check_sub(const stl::fe& a, const stl::fe& b) {
   g_bound_checks++;
-  if (alpha(a) > 3.9 || alpha(b) > 3.9) g_bound_viol++;
+  if (alpha(a) > 3.9 || alpha(b) > 3.9) (*t_bound_viol)++;
 }
 
 static void load8(uint32_t w[8], const uint8_t* p) { std::memcpy(w, p, 32); }
@@ -418,29 +423,27 @@ void hostemu_sc_mul_signed(const uint8_t d_in[20], int d_neg, const uint8_t S_in
 
 uint64_t hostemu_bound_checks(void) { return g_bound_checks.load(); }
 
+#ifndef HOSTEMU_SANITIZE_SUBSET
+// The arithmetic op table (stl_selftest.h) row by row with the bound hooks
+// live: n input rows of kSelftestInWords words, n output rows of
+// kSelftestOutWords words.  Returns the bound violations this call added, or
+// ~0 for an op outside the table.
+uint64_t hostemu_selftest_ops(uint32_t op, const uint32_t* in, size_t n, uint32_t* out) {
+  if (op >= stl::kSelftestOps) return ~0ull;
+  std::atomic<uint64_t> viol{0};
+  t_bound_viol = &viol;
+  for (size_t i = 0; i < n; ++i)
+    stl::selftest_op(op, in + i * stl::kSelftestInWords, out + i * stl::kSelftestOutWords);
+  t_bound_viol = &g_bound_viol;
+  return viol.load();
+}
+#endif  // HOSTEMU_SANITIZE_SUBSET
+
 void hostemu_sha512_hram32(const uint8_t* R, const uint8_t* A, const uint8_t* M, uint8_t out[64]) {
   uint32_t r[8], a[8], m[8], h[16];
   load8(r, R); load8(a, A); load8(m, M);
   stl::sha512_hram32(h, r, a, m);
   std::memcpy(out, h, 64);
-}
-
-void hostemu_sc_reduce64(const uint8_t in[64], uint8_t out[32]) {
-  uint32_t x[16], o[8];
-  std::memcpy(x, in, 64);
-  stl::sc_reduce64(o, x);
-  std::memcpy(out, o, 32);
-}
-
-void hostemu_fe_mul_bytes(const uint8_t a[32], const uint8_t b[32], uint8_t out[32]) {
-  uint32_t wa[8], wb[8], wo[8];
-  load8(wa, a); load8(wb, b);
-  stl::fe fa, fb, fo;
-  stl::fe_frombytes(fa, wa);
-  stl::fe_frombytes(fb, wb);
-  stl::fe_mul(fo, fa, fb);
-  stl::fe_tobytes(wo, fo);
-  std::memcpy(out, wo, 32);
 }
 
 // The wide per-key table j*(-A), j = 0..136, as the two-stage device build
@@ -494,16 +497,6 @@ int hostemu_wide_key_table(const uint8_t A_in[32], uint8_t* out_two_stage, uint8
     cached_affine_bytes(out_direct + 64 * j, d);
   }
   return 1;
-}
-
-void hostemu_fe_invert_bytes(const uint8_t a[32], uint8_t out[32]) {
-  uint32_t wa[8], wo[8];
-  load8(wa, a);
-  stl::fe fa, fo;
-  stl::fe_frombytes(fa, wa);
-  stl::fe_invert(fo, fa);
-  stl::fe_tobytes(wo, fo);
-  std::memcpy(out, wo, 32);
 }
 
 #ifndef HOSTEMU_SANITIZE_SUBSET

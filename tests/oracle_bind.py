@@ -292,4 +292,18 @@ def load_hostemu():
     lib.hostemu_sign_adversarial.argtypes = [V, V, V, V, ctypes.c_size_t, V, V, V]
     lib.hostemu_window_blocks.restype = ctypes.c_uint32
     lib.hostemu_window_blocks.argtypes = [V, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
+    lib.hostemu_selftest_ops.restype = ctypes.c_uint64
+    lib.hostemu_selftest_ops.argtypes = [ctypes.c_uint32, V, ctypes.c_size_t, V]
     return lib
+
+
+def hostemu_selftest_ops(lib, op, rows):
+    """The arithmetic op table (stl_selftest.h) on the host: rows is an
+    (n, 72) uint32 array; returns ((n, 40) uint32 results, bound violations
+    this call added)."""
+    rows = np.ascontiguousarray(rows, np.uint32)
+    assert rows.ndim == 2 and rows.shape[1] == 72
+    out = np.zeros((rows.shape[0], 40), np.uint32)
+    viol = lib.hostemu_selftest_ops(op, _buf(rows), rows.shape[0], _buf(out))
+    assert viol != 2**64 - 1, f"op {op} is not in the table"
+    return out, viol

@@ -113,6 +113,8 @@ def seed_without_overfull_set(ids, sets_log2, first=1):
 
 
 def load_sigcache_emu():
+    from stellard_amd import build
+    build.build_hostemu_sigcache()  # as every other harness: built on load if absent or stale
     lib = ctypes.CDLL(SIGCACHE_SO)
     P, U8 = ctypes.c_void_p, ctypes.c_void_p
     for name, res, args in (
