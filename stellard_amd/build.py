@@ -31,7 +31,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
                 "stl_selftest.hip",
-                "stl_api.cpp",
+                "stl_api.cpp", "stl_api_keyset.cpp", "stl_api_authority.cpp", "stl_api_sigcache.cpp",
                 "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
@@ -39,7 +39,7 @@ PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe2551
                                "stl_hash160.h", "stl_signer_core.h", "stl_signer.h",
                                "stl_acctdir_core.h", "stl_acctdir.h",
                                "stl_sigcache_core.h", "stl_sigcache.h",
-                               "stl_group.h", "stl_selftest.h",
+                               "stl_group.h", "stl_selftest.h", "stl_host.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
 
@@ -67,10 +67,12 @@ def _run(cmd, cwd=ROOT):
     subprocess.run(cmd, cwd=cwd, check=True)
 
 
-# per-object dependencies: the host sources see only the ABI header and the
-# launcher declarations, so a host-side change does not recompile the kernels
+# per-object dependencies: the host sources see only the ABI header, the
+# launcher declarations and their own shared header (HOST_ONLY: no kernel
+# file includes it), so a host-side change does not recompile the kernels
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
-HOST_DEPS = ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
+HOST_ONLY = ["stl_host.h"]
+HOST_DEPS = HOST_ONLY + ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
              "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
@@ -95,7 +97,8 @@ def build_product(force=False, extra_flags=(), variant="variant"):
         if src.endswith(".hip"):
             # each kernel file sees the headers, not the other sources: a change
             # to one leaves the other's object (and code objects) as they are
-            sdeps = [d for d in deps if not d.endswith((".hip", ".cpp")) or d.endswith(src)]
+            sdeps = [d for d in deps
+                     if not d.endswith((".hip", ".cpp", *HOST_ONLY)) or d.endswith(src)]
         else:
             sdeps = [os.path.join(CSRC, d) for d in [src] + HOST_DEPS]
         if force or _stale(obj, sdeps):

@@ -1,8 +1,8 @@
 // stl_api.cpp -- host side of libstl: the extern "C" boundary declared in
-// include/stl.h.  Owns devices, streams, workspaces, staging buffers and RCCL
-// communicators; has no CPU verification path (a device failure returns < 0
-// and the caller -- stellard -- falls back to libsodium, as SURVEY.md
-// section 8b requires).
+// include/stl.h (the handle objects' entry points: stl_api_keyset.cpp,
+// _authority.cpp, _sigcache.cpp).  Owns devices, streams, workspaces, staging
+// buffers and RCCL communicators; has no CPU verification path (a device failure
+// returns < 0 and stellard falls back to libsodium, as SURVEY.md section 8b requires).
 //
 // Threading: stellard calls verify concurrently from JobQueue workers
 // (JobQueue.cpp:217-243).  Every device has a mutex that serialises the host
@@ -19,70 +19,20 @@
 // ones), then one copy brings the bitmap to the host.  One process per GPU
 // uses stl_comm_* + stl_bitmap_gather_device instead.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
-#include <array>
-#include <atomic>
 #include <chrono>
-#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <random>
-#include <set>
 #include <thread>
-#include <vector>
 
-#include "../../include/stl.h"
-#include "stl_kernels.h"
+#include "stl_host.h"
 #include "stl_keycache.h"
-#include "stl_keyset.h"
-#include "stl_keyset_map.h"
-#include "stl_acctdir.h"
-#include "stl_acctdir_core.h"
-#include "stl_signer.h"
-#include "stl_sigcache.h"
-#include "stl_sigcache_core.h"
+#include "stl_keyset.h"  // the miss path's gather and scatter
 
+namespace stl {
 namespace {
-
-// ---- fault injection (stl_debug_fault_after) --------------------------------
-// A countdown over the HIP / RCCL calls libstl checks; the call at which it
-// reaches zero is not executed and reports failure.  One shot.
-std::atomic<long long> g_fault_after{-1};
-
-bool fault_now() {
-  long long v = g_fault_after.load(std::memory_order_relaxed);
-  while (v >= 0) {
-    if (g_fault_after.compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) return v == 0;
-  }
-  return false;
-}
-
-#define STL_TRY(expr)                        \
-  do {                                       \
-    if (fault_now()) return STL_EHIP;        \
-    hipError_t e_ = (expr);                  \
-    if (e_ != hipSuccess) return STL_EHIP;   \
-  } while (0)
-
-#define STL_RCCL_TRY(expr)                   \
-  do {                                       \
-    if (fault_now()) return STL_ERCCL;       \
-    ncclResult_t r_ = (expr);                \
-    if (r_ != ncclSuccess) return STL_ERCCL; \
-  } while (0)
-
-#define STL_RC(expr)        \
-  do {                      \
-    int rc_ = (expr);       \
-    if (rc_) return rc_;    \
-  } while (0)
+std::atomic<long long> g_fault_after{-1};  // the fault countdown (stl_host.h)
 
 // ---- RCCL, loaded on first use (libstl does not need it on one device) ----
 struct Rccl {
@@ -151,133 +101,11 @@ int rccl_settle(ncclComm_t comm, ncclResult_t r) {
   return st == ncclSuccess ? STL_OK : STL_ERCCL;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return STL_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (fault_now() || hipMalloc(&p, bytes) != hipSuccess) {
-      p = nullptr;
-      return STL_ENOMEM;
-    }
-    cap = bytes;
-    return STL_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-// Phase timing (stl_set_phase_timing): launch_verify marks the phase
-// boundaries of each chunk; each mark records a pooled HIP event on the launch
-// stream.  stl_get_stats sums the completed chunks' phase durations.  Timing
-// calls bypass the fault-injection countdown and never fail a launch: a chunk
-// whose events could not be recorded is dropped from the sums.
-struct PhaseTimer {
-  std::mutex mu;
-  std::vector<hipEvent_t> pool;
-  std::vector<std::array<hipEvent_t, 5>> done;
-  uint64_t ns[4] = {0, 0, 0, 0};
-  uint64_t chunks = 0;
-  hipEvent_t take() {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!pool.empty()) {
-      hipEvent_t e = pool.back();
-      pool.pop_back();
-      return e;
-    }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-    return e;
-  }
-  void give(hipEvent_t e) {
-    if (!e) return;
-    std::lock_guard<std::mutex> lk(mu);
-    pool.push_back(e);
-  }
-  // completed chunks -> sums.  A chunk another thread enqueued after the
-  // caller's synchronisation is left in `done` until its last event has
-  // completed (hipEventQuery), so it is neither dropped nor recycled early.
-  void collect() {
-    std::lock_guard<std::mutex> lk(mu);
-    std::vector<std::array<hipEvent_t, 5>> pending;
-    for (auto& c : done) {
-      if (hipEventQuery(c[4]) == hipErrorNotReady) {
-        pending.push_back(c);
-        continue;
-      }
-      uint64_t t[4];
-      bool ok = true;
-      for (int i = 0; i < 4 && ok; ++i) {
-        float ms = 0.f;
-        ok = hipEventElapsedTime(&ms, c[i], c[i + 1]) == hipSuccess;
-        t[i] = (uint64_t)((double)ms * 1e6);
-      }
-      if (ok) {
-        for (int i = 0; i < 4; ++i) ns[i] += t[i];
-        ++chunks;
-      }
-      for (hipEvent_t e : c) pool.push_back(e);
-    }
-    done.swap(pending);
-  }
-  void reset() {
-    collect();
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& v : ns) v = 0;
-    chunks = 0;
-  }
-  void release() {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& c : done)
-      for (hipEvent_t e : c) pool.push_back(e);
-    done.clear();
-    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
-    pool.clear();
-  }
-};
-
 std::atomic<bool> g_phase_timing{false};
 
 // one chunk being marked by this thread (marks of a chunk come from one thread)
 thread_local std::array<hipEvent_t, 5> t_marks;
 thread_local bool t_marks_ok = false;
-
-void phase_mark(void* ctx, hipStream_t s, int i) {
-  auto* t = static_cast<PhaseTimer*>(ctx);
-  if (i == 0) {
-    // events left by a chunk whose launches stopped between its marks (their
-    // timer may be gone after stl_shutdown): destroy them
-    for (hipEvent_t& m : t_marks) {
-      if (m) (void)hipEventDestroy(m);
-      m = nullptr;
-    }
-    t_marks_ok = true;
-  }
-  hipEvent_t e = t->take();
-  if (!e || hipEventRecord(e, s) != hipSuccess) {
-    t->give(e);
-    t_marks[i] = nullptr;
-    t_marks_ok = false;
-  } else {
-    t_marks[i] = e;
-  }
-  if (i == 4) {
-    if (t_marks_ok) {
-      std::lock_guard<std::mutex> lk(t->mu);
-      t->done.push_back(t_marks);
-    } else {
-      for (hipEvent_t m : t_marks) t->give(m);
-    }
-    t_marks.fill(nullptr);
-    t_marks_ok = false;
-  }
-}
 
 // Execution tuning (stl_debug_tuning): how a verify launch is cut into kernels
 // and streams.  Every setting gives the same accept bits (tests run them all).
@@ -331,167 +159,6 @@ uint32_t chunk_for(uint32_t grid, size_t n) {
   return (uint32_t)std::min<size_t>(sub, stl::kPreChunk);
 }
 
-// The verify workspace of one stream: every launch that runs kernels on a
-// stream uses that stream's workspace, in stream order -- the caller's streams
-// (device-resident API) and the library's own pool streams alike, so a pool
-// stream shared by several callers and both APIs needs only one.  `mu` is
-// held while a launch is planned and enqueued (the workspace may grow), and
-// every buffer below is only grown or read under it (the hash
-// queue of a shared pool stream was grown outside it).  Caller streams'
-// contexts are capped per device (kMaxCallerStreams, least recently used
-// evicted) and stl_release_stream drops one: a context lives on in a
-// shared_ptr until its last user returns, then hands its buffers to the
-// device's spare list (CtxSpares) instead of freeing them.  Every use of a
-// caller context ends by recording `done` on its stream (stream_ctx's use
-// token), so a spare's buffers are free once `done` has completed: the next
-// caller context adopts them and makes its stream wait for that event on the
-// device -- no host wait, no hipFree (which would synchronise the whole
-// device: VERDICT r5 #4).
-// Buffers of the keyset calls that take public keys (stl_keyset_*_by_key*), one
-// set per stream context.  A call takes the set out of its context for its
-// whole run (ByKeyLease) -- it enqueues through run_verify, which locks the
-// contexts itself, so it cannot hold the context's mutex to keep a concurrent
-// call on the same stream from growing (freeing) them under its kernels.
-struct ByKeyBufs {
-  DevBuf idx;    // 256 B of counters ([0]: the miss count), key_index (4 B per row), the miss list (4 B per row)
-  DevBuf rows;   // per miss: sig 64 B, msg 32 B, pk 32 B, compact; then their bitmap words
-  DevBuf blob;   // the blob form's verify inputs, 128 B per row (as StreamCtx::scratch)
-  uint32_t* count = nullptr;  // host-mapped word the miss count is copied to
-  hipEvent_t counted = nullptr;  // ... and the event behind that copy
-  bool holds() const { return idx.p || rows.p || blob.p || count || counted; }
-  void release() {
-    idx.release();
-    rows.release();
-    blob.release();
-    if (count) (void)hipHostFree(count);
-    count = nullptr;
-    if (counted) (void)hipEventDestroy(counted);
-    counted = nullptr;
-  }
-};
-
-struct StreamCtx;
-struct CtxSpares {
-  std::mutex mu;
-  std::vector<std::unique_ptr<StreamCtx>> list;  // oldest first
-};
-std::atomic<int>& max_caller_streams();
-struct StreamCtx {
-  std::mutex mu;
-  int ordinal = -1;        // device of the buffers below
-  bool pool = false;       // a library pool stream's context (never evicted)
-  uint64_t last_use = 0;   // LRU tick (Device::ws_mu)
-  // caller contexts: completes after the last work enqueued with this
-  // context's buffers (recorded on the caller's stream after every use)
-  hipEvent_t done = nullptr;
-  std::weak_ptr<CtxSpares> spares;  // where the buffers go when the context dies
-  DevBuf ws;
-  // work counter + longest-first order of the device-resident hash kernels
-  // (stl::hash_queue_bytes(n)) of the launches on this stream
-  DevBuf queue;
-  // fork / join events of launches whose chunks this (caller) stream spreads
-  // over pool streams
-  hipEvent_t fork = nullptr;
-  hipEvent_t join[stl::kMaxVerifyStreams] = {};
-  // a launch's shared key domain is built (stl::VerifyExec::key_ready); the
-  // one-call blob path's two parse kernels are done (the keys are out)
-  hipEvent_t keys = nullptr;
-  hipEvent_t parsed[2] = {};
-  // R decoded ahead for the one-call checkSign's shared key domain
-  // (stl::VerifyExec::rdec: 80 B per row) and its ready event
-  DevBuf rdec;
-  hipEvent_t rready = nullptr;
-  // device-resident automatic dedup: host-mapped word the key sample kernel
-  // writes after each call on this stream (1 = its keys repeated); the next
-  // call reads it without waiting (feedback, so a stale value only picks the
-  // other path -- the bits are the same)
-  uint32_t* auto_flag = nullptr;
-  uint32_t* auto_flag_dev = nullptr;
-  // the device-resident checkSign calls' verify inputs (signing hashes, and
-  // from blobs the signatures and keys), 32 or 128 B per row
-  DevBuf scratch;
-  // the by-key keyset calls' buffers (empty while a call has them out)
-  ByKeyBufs bykey;
-  void release() {
-    if (auto_flag) (void)hipHostFree(auto_flag);
-    auto_flag = auto_flag_dev = nullptr;
-    bykey.release();
-    scratch.release();
-    ws.release();
-    queue.release();
-    for (hipEvent_t& e : join) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    if (fork) (void)hipEventDestroy(fork);
-    fork = nullptr;
-    if (keys) (void)hipEventDestroy(keys);
-    keys = nullptr;
-    for (hipEvent_t& e : parsed) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    rdec.release();
-    if (rready) (void)hipEventDestroy(rready);
-    rready = nullptr;
-    if (done) (void)hipEventDestroy(done);
-    done = nullptr;
-  }
-  bool holds_memory() const {
-    return auto_flag || scratch.p || ws.p || queue.p || fork || keys || parsed[0] || parsed[1] || rdec.p || rready ||
-           done || bykey.holds();
-  }
-  // moves every buffer and event of `o` into this (empty) context
-  void adopt(StreamCtx& o) {
-    std::swap(ws, o.ws);
-    std::swap(queue, o.queue);
-    std::swap(scratch, o.scratch);
-    std::swap(bykey, o.bykey);
-    std::swap(fork, o.fork);
-    std::swap(keys, o.keys);
-    std::swap(parsed[0], o.parsed[0]);
-    std::swap(parsed[1], o.parsed[1]);
-    std::swap(rdec, o.rdec);
-    std::swap(rready, o.rready);
-    for (uint32_t j = 0; j < stl::kMaxVerifyStreams; ++j) std::swap(join[j], o.join[j]);
-    std::swap(auto_flag, o.auto_flag);
-    std::swap(auto_flag_dev, o.auto_flag_dev);
-    std::swap(done, o.done);
-  }
-  ~StreamCtx() {
-    if (!holds_memory() || ordinal < 0) return;
-    // an evicted or released caller context: its buffers go to the device's
-    // spares, to be adopted behind `done` (see above), while the list holds
-    // fewer than the caller-stream cap
-    if (done) {
-      if (std::shared_ptr<CtxSpares> sp = spares.lock()) {
-        auto z = std::make_unique<StreamCtx>();
-        z->ordinal = ordinal;
-        z->adopt(*this);
-        std::unique_ptr<StreamCtx> over;
-        {
-          std::lock_guard<std::mutex> lk(sp->mu);
-          sp->list.push_back(std::move(z));
-          if (sp->list.size() > (size_t)max_caller_streams().load()) {
-            over = std::move(sp->list.front());
-            sp->list.erase(sp->list.begin());
-          }
-        }
-        return;  // `over` (a spare beyond the cap: no spares link) is freed below
-      }
-    }
-    // no spare list (library shut down, or no `done` event): the buffers'
-    // kernels (and the key sample's write to auto_flag) may still be in
-    // flight on a stream the caller may have destroyed since, so wait for the
-    // whole device before freeing
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    if (hipSetDevice(ordinal) == hipSuccess) (void)hipDeviceSynchronize();
-    release();
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 // A spare whose last work has completed if there is one, else the oldest
 // (its adopter's stream waits for it on the device); nullptr if none.
 std::unique_ptr<StreamCtx> take_spare(CtxSpares& sp) {
@@ -508,52 +175,10 @@ std::unique_ptr<StreamCtx> take_spare(CtxSpares& sp) {
   return z;
 }
 
-// Streams ("stream pool"): HIP maps the streams of a
-// process onto GPU_MAX_HW_QUEUES (4 on the pool) hardware queues in creation
-// order, and two streams on one queue run one after another.  So libstl makes
-// exactly three streams per device, in stl_init, in a fixed order -- two
-// kernel streams and one copy stream -- and both APIs share them: the host
-// batch API runs even / odd chunks on `stream` / `stream2` and copies on
-// `copy`; a device-resident call runs its chunks on the caller's stream plus
-// `stream2` (then `stream`).  Made before the caller's later streams, they
-// keep their own queues whatever the caller creates afterwards.
-struct Device {
-  int ordinal = 0;
-  int cus = 0;
-  uint32_t grid = 0;  // resident workgroups for the verify kernel
-  hipStream_t stream = nullptr;   // kernel stream 0: host batch API even chunks and results
-  hipStream_t stream2 = nullptr;  // kernel stream 1: host API odd chunks; a device call's second stream
-  hipStream_t copy = nullptr;     // host-to-device copies (overlap the previous chunk's kernels)
-  // a device call's fourth stream (STL_TUNE_STREAMS 4 only; made on use under
-  // ws_mu, read without a lock by drain / run_verify -- ADVICE r4)
-  std::atomic<hipStream_t> stream3{nullptr};
-  ncclComm_t comm = nullptr;      // in-process communicator (rank = device index)
-  std::mutex mu;
-  DevBuf sig, msg, pk, bitmap, pre, off, len, ctr, ctr2, txid, status, wide, gather;
-  DevBuf counters;  // device u64 counters of stl_get_stats: [0] accepted, [1] full-length lanes,
-                    // [2] / [3] key-cache hits / misses
-  // the decoded-key cache (stl_keycache.h): allocated and zeroed once, in
-  // setup_device (never lazily: a call's memory use stays flat)
-  DevBuf key_cache;
-  int key_cache_log2 = 0;  // log2 of its sets; 0: none
-  // workspace of every stream used: the pool streams' for good, at most
-  // kMaxCallerStreams caller streams' (LRU)
-  std::map<hipStream_t, std::shared_ptr<StreamCtx>> stream_ws;
-  // buffers of evicted / released caller contexts, adopted by the next ones
-  std::shared_ptr<CtxSpares> spares = std::make_shared<CtxSpares>();
-  uint64_t ws_tick = 0;
-  std::mutex ws_mu;
-  void* stage = nullptr;  // pinned host staging of small host batches (run_small), under mu
-  size_t stage_cap = 0;
-  PhaseTimer timer;
-  stl::PhaseClock clock{phase_mark, &timer};
-};
-
 // the device's phase clock when timing is on, else none
 const stl::PhaseClock* phase_clock(Device& d) { return g_phase_timing.load() ? &d.clock : nullptr; }
 
 std::mutex g_mu;
-std::vector<std::unique_ptr<Device>> g_devs;
 bool g_init = false;
 int g_shards_per_device = 1;
 bool g_comm_gather = false;  // host batches gather their bitmap over RCCL
@@ -589,12 +214,61 @@ void mark_gather_start(hipStream_t s) {
   g_gather_stream = hipEventRecord(g_gather_start, s) == hipSuccess ? s : nullptr;
 }
 
-unsigned long long* dev_counters(Device& d) { return static_cast<unsigned long long*>(d.counters.p); }
-
 // ---- host-side statistics (stl_get_stats) and tracing (STL_TRACE=1) ----
 std::atomic<uint64_t> g_st_batches{0}, g_st_sigs{0}, g_st_errors{0}, g_st_host_ns{0}, g_st_gather_ns{0},
     g_st_auto_dedup{0};
 bool g_trace = false;
+}  // namespace
+
+std::vector<std::unique_ptr<Device>> g_devs;
+
+bool fault_now() {
+  long long v = g_fault_after.load(std::memory_order_relaxed);
+  while (v >= 0) {
+    if (g_fault_after.compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) return v == 0;
+  }
+  return false;
+}
+
+void phase_mark(void* ctx, hipStream_t s, int i) {
+  auto* t = static_cast<PhaseTimer*>(ctx);
+  if (i == 0) {
+    // events left by a chunk whose launches stopped between its marks (their
+    // timer may be gone after stl_shutdown): destroy them
+    for (hipEvent_t& m : t_marks) {
+      if (m) (void)hipEventDestroy(m);
+      m = nullptr;
+    }
+    t_marks_ok = true;
+  }
+  hipEvent_t e = t->take();
+  if (!e || hipEventRecord(e, s) != hipSuccess) {
+    t->give(e);
+    t_marks[i] = nullptr;
+    t_marks_ok = false;
+  } else {
+    t_marks[i] = e;
+  }
+  if (i == 4) {
+    if (t_marks_ok) {
+      std::lock_guard<std::mutex> lk(t->mu);
+      t->done.push_back(t_marks);
+    } else {
+      for (hipEvent_t m : t_marks) t->give(m);
+    }
+    t_marks.fill(nullptr);
+    t_marks_ok = false;
+  }
+}
+
+unsigned long long* dev_counters(Device& d) { return static_cast<unsigned long long*>(d.counters.p); }
+
+int check_flags(uint32_t flags) {
+  return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_FULL_LENGTH | STL_DEDUP_KEYS | STL_ONE_LANE |
+                    STL_NO_AUTO_DEDUP | STL_DEBUG_RAW_PREDICATE))
+             ? STL_EINVAL
+             : STL_OK;
+}
 
 uint64_t now_ns() {
   return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -602,39 +276,20 @@ uint64_t now_ns() {
       .count();
 }
 
-// Counts one host entry-point call: signatures, wall time, errors; with
-// STL_TRACE=1 one JSON line per call on stderr (host spans; the kernels are
-// rocprofv3's).
-struct CallSpan {
-  const char* name;
-  size_t n;
-  uint64_t t0 = now_ns();
-  int finish(int rc, uint64_t gather_ns = 0) {
-    const uint64_t dt = now_ns() - t0;
-    g_st_batches++;
-    g_st_sigs += n;
-    g_st_host_ns += dt;
-    g_st_gather_ns += gather_ns;
-    if (rc < 0) g_st_errors++;
-    if (g_trace)
-      std::fprintf(stderr, "{\"stl_trace\": \"%s\", \"n\": %zu, \"rc\": %d, \"ms\": %.3f, \"gather_ms\": %.3f}\n", name, n,
-                   rc, dt * 1e-6, gather_ns * 1e-6);
-    return rc;
-  }
-};
+int CallSpan::finish(int rc, uint64_t gather_ns) {
+  const uint64_t dt = now_ns() - t0;
+  g_st_batches++;
+  g_st_sigs += n;
+  g_st_host_ns += dt;
+  g_st_gather_ns += gather_ns;
+  if (rc < 0) g_st_errors++;
+  if (g_trace)
+    std::fprintf(stderr, "{\"stl_trace\": \"%s\", \"n\": %zu, \"rc\": %d, \"ms\": %.3f, \"gather_ms\": %.3f}\n", name, n,
+                 rc, dt * 1e-6, gather_ns * 1e-6);
+  return rc;
+}
 
-// Restores the calling thread's current HIP device on scope exit: the host
-// entry points switch devices internally, and a library call must not leave
-// the caller (stellard, or a PyTorch user of the device API) on another one.
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
+namespace {
 
 int current_device_index() {
   int ord = -1;
@@ -719,14 +374,6 @@ void release_device(Device& d) {
   d.stream3.store(nullptr);
 }
 
-int ensure_init() {
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (g_init) return STL_OK;
-  }
-  return stl_init(nullptr);
-}
-
 // Caller streams whose contexts a device keeps: each holds a
 // verify workspace (stl::verify_ws_bytes: ~0.44 GB, ~0.7 GB with key dedup),
 // so a caller cycling through many streams must not grow device memory
@@ -736,7 +383,6 @@ int ensure_init() {
 // with room to spare -- 8 contexts hold <= 5.6 GB of the 288 GB.
 constexpr int kDefaultCallerStreams = 8;
 std::atomic<int> g_max_caller_streams{kDefaultCallerStreams};
-std::atomic<int>& max_caller_streams() { return g_max_caller_streams; }
 
 bool is_pool_stream(const Device& d, hipStream_t s) {
   return s && (s == d.stream || s == d.stream2 || s == d.copy || s == d.stream3.load());
@@ -755,6 +401,17 @@ struct CtxUse {
     (void)hipEventRecord(c->done, s);
   }
 };
+}  // namespace
+
+int ensure_init() {
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_init) return STL_OK;
+  }
+  return stl_init(nullptr);
+}
+
+std::atomic<int>& max_caller_streams() { return g_max_caller_streams; }
 
 // The context of stream s on device d (created on first use).  Creating a
 // caller stream's context beyond the cap evicts the least recently used
@@ -814,6 +471,8 @@ std::shared_ptr<StreamCtx> stream_ctx(Device& d, hipStream_t s) {
   return std::shared_ptr<StreamCtx>(use, use->c.get());
 }
 
+namespace {
+
 // Caller contexts currently kept on device d (tests: the cap holds).
 int caller_contexts(Device& d) {
   std::lock_guard<std::mutex> lk(d.ws_mu);
@@ -838,9 +497,6 @@ uint32_t pair_max(const Device& d) { return pair_max_lanes(d.grid); }
 // measured slower than lane pairs; STL_TUNE_QUAD bits 0 / 1 turn them on).
 uint32_t quad_max(const Device& d) { return (g_tune_quad.load() & 1) ? d.grid * stl::kBlock / 16 : 0u; }
 uint32_t duo_max(const Device& d) { return (g_tune_quad.load() & 2) ? d.grid * stl::kBlock / 8 : 0u; }
-
-unsigned long long* dev_counters(Device& d);
-const stl::PhaseClock* phase_clock(Device& d);
 
 // A pool kernel stream that a call running on streams[0..S) does not use:
 // the shared key domain is built there, beside the chunks' scalar kernels
@@ -939,7 +595,8 @@ int run_verify(Device& d, hipStream_t s, const uint8_t* sig, const uint8_t* msg_
 // Hash work queue of stream context c for n rows (counter + longest-first
 // order, stl::hash_queue_bytes(n)).  Caller holds c.mu until the hash kernel
 // using it is enqueued (a concurrent grow would free it first -- ADVICE r4).
-int ctx_queue(StreamCtx& c, size_t n, uint32_t** qws, bool blob = false) {
+}  // namespace
+int ctx_queue(StreamCtx& c, size_t n, uint32_t** qws, bool blob) {
   STL_RC(c.queue.ensure(blob ? stl::blob_queue_bytes(n) : stl::hash_queue_bytes(n)));
   *qws = static_cast<uint32_t*>(c.queue.p);
   return STL_OK;
@@ -956,6 +613,8 @@ uint32_t hash_long_min(const Device& d, size_t n) {
   return n <= 2 * (size_t)pair_max(d) ? (uint32_t)g_tune_long_hash.load() : 0u;
 }
 
+namespace {
+
 uint32_t grid_for(const Device& d, size_t n) {
   const size_t tiles = (n + stl::kBlock - 1) / stl::kBlock;
   return (uint32_t)std::max<size_t>(1, std::min<size_t>(tiles, d.grid));
@@ -968,7 +627,6 @@ void shard(size_t n, int r, int g, size_t* lo, size_t* hi) {
   *lo = std::min(n, (size_t)r * per * 64);
   *hi = std::min(n, (size_t)(r + 1) * per * 64);
 }
-
 
 // Byte-balanced 64-aligned shard boundaries: bound[r] = the 64-aligned row at
 // or after the first row whose byte prefix sum reaches r/g of the total --
@@ -1303,13 +961,6 @@ int gather_to_host(const Batch& b, std::vector<Shard>& sh, size_t n, size_t per,
   return STL_OK;
 }
 
-int check_flags(uint32_t flags) {
-  return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_FULL_LENGTH | STL_DEDUP_KEYS | STL_ONE_LANE |
-                    STL_NO_AUTO_DEDUP | STL_DEBUG_RAW_PREDICATE))
-             ? STL_EINVAL
-             : STL_OK;
-}
-
 // Host batches choose key dedup per chunk unless the caller decided
 // (STL_DEDUP_KEYS on, STL_NO_AUTO_DEDUP off) or the chunk runs on lane pairs.
 bool auto_dedup(uint32_t flags) {
@@ -1428,64 +1079,57 @@ int env_int(const char* name, int dflt) {
   const char* v = std::getenv(name);
   return (v && *v) ? std::atoi(v) : dflt;
 }
-
 }  // namespace
 
-// ---- registered signer sets (stl_keyset_*) ----
-// One keyset: the keys (host), their first-index map, and on one device the
-// records and tables of its nkeys keys plus the base point's (stl_keyset.h).
-struct stl_keyset {
-  int ordinal = -1;
-  uint32_t nkeys = 0;
-  std::vector<uint8_t> pk;
-  std::map<std::array<uint8_t, 32>, uint32_t> first;
-  DevBuf rec, tables;
-  // the key -> first index map for the device (stl_keyset_map.h): built from
-  // `first`, with the seed and longest probe sequence the builder settled on
-  // (map_bound: the bound it had to keep), and its copy on the device
-  stl::KeysetMap map;
-  uint32_t map_bound = stl::kKsMapProbeBound;
-  DevBuf map_dev;
-  stl::KeysetMapDev d_map() const {
-    return stl::KeysetMapDev{static_cast<const uint32_t*>(map_dev.p), map.mask(), map.longest, map.seed};
+LiveSetBase* LiveSetBase::head = nullptr;
+
+// ---- the synchronous host call (stl_host.h) ----
+int HostCall::upload(DevBuf& b, const void* src, size_t bytes) {
+  STL_RC(b.ensure(bytes));
+  STL_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, d.stream));
+  return STL_OK;
+}
+
+int HostCall::rows(const uint8_t* bytes, const uint64_t* off, const uint32_t* len, size_t n) {
+  uint64_t base = 0, span_bytes = 0;
+  rebase(off, len, 0, n, roff_, row_end_, &base, &span_bytes);
+  STL_RC(d.pre.ensure(span_bytes + 16));
+  if (span_bytes) STL_TRY(hipMemcpyAsync(d.pre.p, bytes + base, span_bytes, hipMemcpyHostToDevice, d.stream));
+  STL_RC(upload(d.off, roff_.data(), n * 8));
+  return upload(d.len, len, n * 4);
+}
+
+int HostCall::fetch() {
+  size_t total = 0;
+  for (const Out& o : outs_) total += o.bytes;
+  bounce_.resize(total);
+  uint8_t* at = bounce_.data();
+  for (const Out& o : outs_) {
+    STL_TRY(hipMemcpyAsync(at, o.b->p, o.bytes, hipMemcpyDeviceToHost, d.stream));
+    at += o.bytes;
   }
-  size_t table_bytes() const { return ((size_t)nkeys + 1) * stl::keyset_key_words() * 4; }
-  const uint32_t* d_rec() const { return static_cast<const uint32_t*>(rec.p); }
-  const uint32_t* d_tables() const { return static_cast<const uint32_t*>(tables.p); }
-};
-
-namespace {
-// The live keysets.  g_ks_mu is held while a call looks its handle up and
-// enqueues its kernels, and while a keyset is destroyed -- so a handle that
-// passed the lookup stays alive until its work is on the stream, and destroy
-// (which then waits for the device) sees all of it.  Lock order: g_ks_mu
-// before g_mu / a device's mu / a stream context's mu.
-std::mutex g_ks_mu;
-std::set<const stl_keyset*> g_keysets;
-
-// Waits for the device, then frees the keyset (g_ks_mu held, ks registered).
-void keyset_free_locked(stl_keyset* ks) {
-  g_keysets.erase(ks);
-  DeviceGuard guard;
-  if (hipSetDevice(ks->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
-  ks->rec.release();
-  ks->tables.release();
-  ks->map_dev.release();
-  delete ks;
+  STL_TRY(hipStreamSynchronize(d.stream));
+  return STL_OK;
 }
 
-void keysets_release_all() {
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  while (!g_keysets.empty()) keyset_free_locked(const_cast<stl_keyset*>(*g_keysets.begin()));
+int HostCall::run(const std::function<int()>& body) {
+  int rc = fault_now() || hipSetDevice(d.ordinal) != hipSuccess ? STL_EHIP : body();
+  if (!rc) rc = fetch();
+  if (rc) {  // nothing may still read the caller's rows or write the bounce buffer
+    (void)hipStreamSynchronize(d.stream);
+    return span.finish(rc);
+  }
+  const uint8_t* at = bounce_.data();
+  for (const Out& o : outs_) {
+    std::memcpy(o.dst, at, o.bytes);
+    at += o.bytes;
+  }
+  return span.finish(STL_OK);
 }
 
-void acctdirs_release_all();  // the account directories, further down
-void sigcaches_release_all();  // the verified-ID caches, further down
+}  // namespace stl
 
-int check_keyset_flags(uint32_t flags) {
-  return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_DEBUG_RAW_PREDICATE)) ? STL_EINVAL : STL_OK;
-}
-}  // namespace
+using namespace stl;
 
 extern "C" {
 
@@ -1590,9 +1234,7 @@ int stl_init(const stl_config* cfg) {
 
 void stl_shutdown(void) {
   stl_comm_destroy();
-  keysets_release_all();
-  acctdirs_release_all();
-  sigcaches_release_all();
+  LiveSetBase::release_every();
   DeviceGuard guard;
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto& d : g_devs) {
@@ -1943,7 +1585,9 @@ int verify_detached_device(const uint8_t* sig, const uint8_t* m, unsigned long l
 }
 }  // namespace
 
-namespace {
+}  // extern "C"
+
+namespace stl {
 int device_for_call(Device** out) {
   STL_RC(ensure_init());
   const int di = current_device_index();
@@ -1951,9 +1595,17 @@ int device_for_call(Device** out) {
   *out = g_devs[di].get();
   return STL_OK;
 }
-}  // namespace
 
 namespace {
+// One 64-byte host-mapped, coherent allocation: a word a kernel or a copy
+// writes and the host reads without a synchronising call.
+int mapped_word(uint32_t** out) {
+  void* p = nullptr;
+  STL_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
+  *out = static_cast<uint32_t*>(p);
+  return STL_OK;
+}
+
 // The device-resident calls' automatic dedup: the keys are in
 // HBM, so instead of reading them on the host each call ends with a
 // one-workgroup sample kernel on the caller's stream whose verdict the NEXT
@@ -1967,13 +1619,11 @@ int auto_dedup_device(StreamCtx& c, uint32_t flags, uint32_t* mode, uint32_t** f
   if (!auto_dedup(flags)) return STL_OK;
   std::lock_guard<std::mutex> lk(c.mu);
   if (!c.auto_flag) {
-    void* p = nullptr;
-    STL_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    c.auto_flag = static_cast<uint32_t*>(p);
+    STL_RC(mapped_word(&c.auto_flag));
     *c.auto_flag = 0;
     void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) {
-      (void)hipHostFree(p);
+    if (hipHostGetDevicePointer(&dp, c.auto_flag, 0) != hipSuccess) {
+      (void)hipHostFree(c.auto_flag);
       c.auto_flag = nullptr;
       return STL_EHIP;
     }
@@ -1987,6 +1637,45 @@ int auto_dedup_device(StreamCtx& c, uint32_t flags, uint32_t* mode, uint32_t** f
   return STL_OK;
 }
 }  // namespace
+
+int blob_prepare(Device& d, StreamCtx& c, uint32_t kind, const uint8_t* d_blobs, const uint64_t* d_offset,
+                 const uint32_t* d_len, size_t n, uint8_t* d_msg, uint8_t* d_sig, uint8_t* d_pk, uint8_t* d_id,
+                 uint8_t* d_status, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(c.mu);
+  uint32_t* ctr = nullptr;
+  STL_RC(ctx_queue(c, n, &ctr, true));
+  STL_TRY(stl::launch_tx_blob(d_blobs, d_offset, d_len, (uint32_t)n, d_msg, d_sig, d_pk, d_id, d_status, ctr,
+                              hash_grid(d), s, kind));
+  return STL_OK;
+}
+
+int miss_counters(ByKeyBufs& b, size_t idx_bytes) {
+  STL_RC(b.idx.ensure(idx_bytes));
+  if (!b.count) STL_RC(mapped_word(&b.count));
+  if (!b.counted) STL_TRY(hipEventCreateWithFlags(&b.counted, hipEventDisableTiming));
+  return STL_OK;
+}
+
+int verify_misses(Device& d, ByKeyLease& use, const uint32_t* miss_rows, size_t m, const uint8_t* d_sig,
+                  const uint8_t* d_msg, const uint8_t* d_pk, uint64_t* d_words, uint32_t flags, hipStream_t s,
+                  const uint64_t** compact_words) {
+  const size_t csig = 0, cmsg = align256(m * 64), cpk = cmsg + align256(m * 32), cwords = cpk + align256(m * 32);
+  STL_RC(use.b.rows.ensure(cwords + (m + 63) / 64 * 8));
+  uint8_t* r = static_cast<uint8_t*>(use.b.rows.p);
+  uint64_t* words = reinterpret_cast<uint64_t*>(r + cwords);
+  if (compact_words) *compact_words = words;
+  STL_TRY(stl::launch_keyset_gather_rows(miss_rows, (uint32_t)m, d_sig, d_msg, d_pk, r + csig, r + cmsg, r + cpk, s));
+  uint32_t mode = stl::kernel_mode(flags);
+  uint32_t* flag_dev = nullptr;
+  STL_RC(auto_dedup_device(*use.c, flags, &mode, &flag_dev));
+  STL_RC(run_verify(d, s, r + csig, r + cmsg, r + cpk, m, words, mode, false, g_tune_streams.load()));
+  if (flag_dev) STL_TRY(stl::launch_key_sample(r + cpk, (uint32_t)m, flag_dev, s));
+  STL_TRY(stl::launch_keyset_scatter_bits(miss_rows, (uint32_t)m, words, d_words, s));
+  return STL_OK;
+}
+}  // namespace stl
+
+extern "C" {
 
 namespace {
 // Device-resident checkSign (SURVEY 8a rows a5-a6 over rows already in HBM):
@@ -2341,13 +2030,7 @@ int stl_signed_blob_prepare_device(uint32_t kind, const uint8_t* d_blobs, const 
   Device* d = nullptr;
   STL_RC(device_for_call(&d));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const std::shared_ptr<StreamCtx> c = stream_ctx(*d, s);
-  std::lock_guard<std::mutex> lk(c->mu);
-  uint32_t* ctr = nullptr;
-  STL_RC(ctx_queue(*c, n, &ctr, true));
-  STL_TRY(stl::launch_tx_blob(d_blobs, d_offset, d_len, (uint32_t)n, d_msg, d_sig, d_pk, d_id, d_status, ctr,
-                              hash_grid(*d), s, kind));
-  return STL_OK;
+  return blob_prepare(*d, *stream_ctx(*d, s), kind, d_blobs, d_offset, d_len, n, d_msg, d_sig, d_pk, d_id, d_status, s);
 }
 
 int stl_tx_blob_prepare_device(const uint8_t* d_blobs, const uint64_t* d_offset, const uint32_t* d_len, size_t n,
@@ -2564,1044 +2247,6 @@ int stl_bitmap_gatherv_device(const uint64_t* d_words, size_t nwords, uint64_t* 
   const int erc = rccl_settle(g_pcomm, g_rccl.GroupEnd());
   if (erc) pcomm_abort_locked();  // failed or timed out: the communicator is unusable
   return rc ? rc : erc;
-}
-
-// ---- registered signer sets ----
-namespace {
-// B's encoding (y = 4/5, x positive): the base point's table is built by the
-// keys' kernels from it
-void base_point_bytes(uint8_t out[32]) {
-  std::memset(out, 0x66, 32);
-  out[0] = 0x58;
-}
-
-// Decodes the keys and builds the tables of `ks` on d.stream (d.mu held).
-// `all` (the keys and B's encoding, the copy's source), dpk and scratch are
-// the caller's: they outlive the stream's work also when a call here fails.
-int keyset_build(Device& d, stl_keyset& ks, std::vector<uint8_t>& all, DevBuf& dpk, DevBuf& scratch) {
-  const uint32_t nk = ks.nkeys;
-  STL_TRY(hipSetDevice(d.ordinal));
-  STL_RC(ks.rec.ensure(((size_t)nk + 1) * stl::keyset_rec_words() * 4));
-  STL_RC(ks.tables.ensure(ks.table_bytes()));
-  STL_RC(dpk.ensure(((size_t)nk + 1) * 32));
-  // the build runs `step` keys at a time: the normalisation's scratch stays small
-  const uint32_t step = std::min<uint32_t>(nk + 1, 512);
-  STL_RC(scratch.ensure((size_t)step * stl::keyset_scratch_words_per_key() * 4));
-  all = ks.pk;
-  all.resize(((size_t)nk + 1) * 32);
-  base_point_bytes(&all[(size_t)nk * 32]);
-  STL_RC(ks.map_dev.ensure(ks.map.slots.size() * 4));
-  STL_TRY(hipMemcpyAsync(dpk.p, all.data(), all.size(), hipMemcpyHostToDevice, d.stream));
-  // the map goes up with the records (ks.map.slots is the keyset's own: it outlives the copy)
-  STL_TRY(hipMemcpyAsync(ks.map_dev.p, ks.map.slots.data(), ks.map.slots.size() * 4, hipMemcpyHostToDevice, d.stream));
-  STL_TRY(hipMemsetAsync(ks.tables.p, 0, ks.table_bytes(), d.stream));
-  STL_TRY(stl::launch_keyset_decode(static_cast<const uint8_t*>(dpk.p), nk, static_cast<uint32_t*>(ks.rec.p), d.stream));
-  for (uint32_t first = 0; first <= nk; first += step)
-    STL_TRY(stl::launch_keyset_build(ks.d_rec(), first, std::min<uint32_t>(step, nk + 1 - first),
-                                     static_cast<uint32_t*>(ks.tables.p), static_cast<uint32_t*>(scratch.p),
-                                     d.stream));
-  STL_TRY(hipStreamSynchronize(d.stream));
-  return STL_OK;
-}
-
-// The live keyset of a handle on the calling thread's device (g_ks_mu held).
-int keyset_for_call(const stl_keyset* ks, Device** d) {
-  if (!ks || !g_keysets.count(ks)) return STL_EINVAL;
-  STL_RC(device_for_call(d));
-  return (*d)->ordinal == ks->ordinal ? STL_OK : STL_EINVAL;
-}
-
-int keyset_launch(Device& d, const stl_keyset& ks, const uint32_t* d_key_index, const uint8_t* d_sig,
-                  const uint8_t* d_msg, size_t n, uint64_t* d_words, uint32_t flags, hipStream_t s) {
-  STL_TRY(stl::launch_keyset_verify(d_sig, d_msg, d_key_index, (uint32_t)n, ks.d_rec(), ks.d_tables(), ks.nkeys,
-                                    stl::core_policy(stl::kernel_mode(flags)), d_words, dev_counters(d), s));
-  return STL_OK;
-}
-
-// ---- verify by public key ----
-// One call's hold on its stream context's by-key buffers: taken out of the
-// context under its mutex, put back the same way.  Should a concurrent call on
-// the same stream have put its own set back first, the larger of the two stays
-// and the other is freed once the stream has drained.
-struct ByKeyLease {
-  std::shared_ptr<StreamCtx> c;
-  hipStream_t s;
-  ByKeyBufs b;
-  ByKeyLease(std::shared_ptr<StreamCtx> ctx, hipStream_t stream) : c(std::move(ctx)), s(stream) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    std::swap(b, c->bykey);
-  }
-  ~ByKeyLease() {
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      if (b.idx.cap + b.rows.cap + b.blob.cap >= c->bykey.idx.cap + c->bykey.rows.cap + c->bykey.blob.cap)
-        std::swap(b, c->bykey);
-    }
-    if (!b.holds()) return;
-    (void)hipStreamSynchronize(s);
-    b.release();
-  }
-  ByKeyLease(const ByKeyLease&) = delete;
-  ByKeyLease& operator=(const ByKeyLease&) = delete;
-};
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// The by-key verify of n rows on stream s (kl: g_ks_mu, held; ks live on d).
-// Lookup with the miss list, the count copied to the lease's host-mapped word
-// behind an event; the keyset verify of all n rows is enqueued; then the one
-// wait -- for that event, with g_ks_mu released: from here on the keyset is
-// not touched again -- and the rows that missed go through run_verify,
-// compacted, their bits ORed back.
-int keyset_by_key(std::unique_lock<std::mutex>& kl, Device& d, const stl_keyset& ks, ByKeyLease& use,
-                  const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg, size_t n, uint64_t* d_words,
-                  uint32_t flags, hipStream_t s, size_t* misses) {
-  ByKeyBufs& b = use.b;
-  const size_t list = align256(n * 4);
-  STL_RC(b.idx.ensure(256 + 2 * list));
-  if (!b.count) {
-    void* p = nullptr;
-    STL_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    b.count = static_cast<uint32_t*>(p);
-  }
-  if (!b.counted) STL_TRY(hipEventCreateWithFlags(&b.counted, hipEventDisableTiming));
-  uint8_t* base = static_cast<uint8_t*>(b.idx.p);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(base);
-  uint32_t* key_index = reinterpret_cast<uint32_t*>(base + 256);
-  uint32_t* miss_rows = reinterpret_cast<uint32_t*>(base + 256 + list);
-  STL_TRY(hipMemsetAsync(cnt, 0, 4, s));
-  STL_TRY(stl::launch_keyset_lookup(d_pk, (uint32_t)n, ks.d_map(), ks.d_rec(), key_index, miss_rows, cnt, s));
-  STL_TRY(hipMemcpyAsync(b.count, cnt, 4, hipMemcpyDeviceToHost, s));
-  STL_TRY(hipEventRecord(b.counted, s));
-  STL_RC(keyset_launch(d, ks, key_index, d_sig, d_msg, n, d_words, flags, s));
-  kl.unlock();
-  STL_TRY(hipEventSynchronize(b.counted));
-  const size_t m = __atomic_load_n(b.count, __ATOMIC_ACQUIRE);
-  if (m > n) return STL_EHIP;
-  if (misses) *misses = m;
-  if (m == 0) return STL_OK;
-  const size_t csig = 0, cmsg = align256(m * 64), cpk = cmsg + align256(m * 32), cwords = cpk + align256(m * 32);
-  STL_RC(b.rows.ensure(cwords + (m + 63) / 64 * 8));
-  uint8_t* r = static_cast<uint8_t*>(b.rows.p);
-  STL_TRY(stl::launch_keyset_gather_rows(miss_rows, (uint32_t)m, d_sig, d_msg, d_pk, r + csig, r + cmsg, r + cpk, s));
-  // the mode the flags give, as stl_ed25519_verify_batch_device runs them: the
-  // keyset flags leave the key dedup to the stream's automatic choice (signers
-  // outside the set repeat as well), sampled on the compact keys
-  uint32_t mode = stl::kernel_mode(flags);
-  uint32_t* flag_dev = nullptr;
-  STL_RC(auto_dedup_device(*use.c, flags, &mode, &flag_dev));
-  STL_RC(run_verify(d, s, r + csig, r + cmsg, r + cpk, m, reinterpret_cast<uint64_t*>(r + cwords), mode, false,
-                    g_tune_streams.load()));
-  if (flag_dev) STL_TRY(stl::launch_key_sample(r + cpk, (uint32_t)m, flag_dev, s));
-  STL_TRY(stl::launch_keyset_scatter_bits(miss_rows, (uint32_t)m, reinterpret_cast<const uint64_t*>(r + cwords),
-                                          d_words, s));
-  return STL_OK;
-}
-}  // namespace
-
-int stl_keyset_create(const uint8_t* pk, size_t nkeys, uint32_t flags, stl_keyset** out) {
-  if (out) *out = nullptr;
-  if (!pk || !out || nkeys == 0 || nkeys > STL_KEYSET_MAX_KEYS || flags != 0) return STL_EINVAL;
-  Device* d = nullptr;
-  STL_RC(device_for_call(&d));
-  std::unique_ptr<stl_keyset> ks(new stl_keyset());
-  ks->ordinal = d->ordinal;
-  ks->nkeys = (uint32_t)nkeys;
-  ks->pk.assign(pk, pk + nkeys * 32);
-  for (size_t i = 0; i < nkeys; ++i) {
-    std::array<uint8_t, 32> a;
-    std::memcpy(a.data(), pk + 32 * i, 32);
-    ks->first.emplace(a, (uint32_t)i);  // keeps the first index of a duplicate
-  }
-  {
-    // the device's map, from `first`: a lookup there answers as stl_keyset_find
-    std::vector<uint32_t> firsts;
-    firsts.reserve(ks->first.size());
-    for (const auto& kv : ks->first) firsts.push_back(kv.second);
-    std::sort(firsts.begin(), firsts.end());
-    std::vector<uint32_t> words(nkeys * 8);
-    std::memcpy(words.data(), pk, nkeys * 32);
-    if (!stl::keyset_map_build(ks->map, words.data(), (uint32_t)nkeys, firsts.data(), (uint32_t)firsts.size()))
-      return STL_EINVAL;  // no seed keeps the probe bound: not reachable by keys that were not made for it
-  }
-  DeviceGuard guard;
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(d->mu);
-    DevBuf dpk, scratch;
-    std::vector<uint8_t> all;
-    rc = keyset_build(*d, *ks, all, dpk, scratch);
-    if (rc) (void)hipStreamSynchronize(d->stream);  // nothing may still run on the buffers freed below
-    dpk.release();
-    scratch.release();
-    if (rc) {
-      ks->rec.release();
-      ks->tables.release();
-      ks->map_dev.release();
-    }
-  }
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  g_keysets.insert(ks.get());
-  *out = ks.release();
-  return STL_OK;
-}
-
-void stl_keyset_destroy(stl_keyset* ks) {
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  if (ks && g_keysets.count(ks)) keyset_free_locked(ks);
-}
-
-int stl_keyset_get_info(const stl_keyset* ks, stl_keyset_info* out) {
-  if (!out || out->struct_size != sizeof(stl_keyset_info)) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  if (!ks || !g_keysets.count(ks)) return STL_EINVAL;
-  const stl::KeysetGeometry g = stl::keyset_geometry();
-  out->nkeys = ks->nkeys;
-  out->window_bits = g.window_bits;
-  out->windows = g.windows;
-  out->rows_per_window = g.rows_per_window;
-  out->row_bytes = g.row_bytes;
-  out->device = ks->ordinal;
-  out->reserved = 0;
-  out->table_bytes = ks->table_bytes();
-  return STL_OK;
-}
-
-long long stl_keyset_find(const stl_keyset* ks, const uint8_t pk[32]) {
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  if (!ks || !pk || !g_keysets.count(ks)) return -1;
-  std::array<uint8_t, 32> a;
-  std::memcpy(a.data(), pk, 32);
-  const auto it = ks->first.find(a);
-  return it == ks->first.end() ? -1 : (long long)it->second;
-}
-
-int stl_keyset_verify_batch_device(stl_keyset* ks, const uint32_t* d_key_index, const uint8_t* d_sig,
-                                   const uint8_t* d_msg, size_t n, uint64_t* d_bitmap_words, uint32_t flags,
-                                   void* stream) {
-  if (!ks) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull || (n && (!d_key_index || !d_sig || !d_msg || !d_bitmap_words))) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  if (n == 0) return STL_OK;
-  return keyset_launch(*d, *ks, d_key_index, d_sig, d_msg, n, d_bitmap_words, flags, static_cast<hipStream_t>(stream));
-}
-
-int stl_keyset_tx_verify_batch_device(stl_keyset* ks, const uint32_t* d_key_index, const uint8_t* d_preimages,
-                                      const uint64_t* d_offset, const uint32_t* d_len, const uint8_t* d_sig, size_t n,
-                                      uint64_t* d_bitmap_words, uint32_t flags, void* stream) {
-  if (!ks) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull ||
-      (n && (!d_key_index || !d_preimages || !d_offset || !d_len || !d_sig || !d_bitmap_words)))
-    return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  if (n == 0) return STL_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const std::shared_ptr<StreamCtx> c = stream_ctx(*d, s);
-  std::lock_guard<std::mutex> cl(c->mu);
-  uint32_t* ctr = nullptr;
-  STL_RC(ctx_queue(*c, n, &ctr));
-  STL_RC(c->scratch.ensure(n * 32));  // the signing hashes
-  uint8_t* msg = static_cast<uint8_t*>(c->scratch.p);
-  STL_TRY(stl::launch_tx_hash(d_preimages, d_offset, d_len, (uint32_t)n, msg, ctr, hash_grid(*d), s,
-                              hash_long_min(*d, n)));
-  return keyset_launch(*d, *ks, d_key_index, d_sig, msg, n, d_bitmap_words, flags, s);
-}
-
-int stl_keyset_verify_batch(stl_keyset* ks, const uint32_t* key_index, const uint8_t* sig, const uint8_t* msg,
-                            size_t n, uint8_t* accept_bitmap, uint32_t flags) {
-  if (!ks) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull || (n && (!key_index || !sig || !msg || !accept_bitmap))) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  Device* dp = nullptr;
-  STL_RC(keyset_for_call(ks, &dp));
-  if (n == 0) return STL_OK;
-  for (size_t i = 0; i < n; ++i)
-    if (key_index[i] >= ks->nkeys) return STL_EINVAL;
-  CallSpan span{"stl_keyset_verify_batch", n};
-  Device& d = *dp;
-  std::lock_guard<std::mutex> dl(d.mu);
-  const size_t words = (n + 63) / 64;
-  std::vector<uint64_t> host_words(words);
-  auto go = [&]() -> int {
-    STL_RC(d.sig.ensure(n * 64));
-    STL_RC(d.msg.ensure(n * 32));
-    STL_RC(d.len.ensure(n * 4));
-    STL_RC(d.bitmap.ensure(words * 8));
-    STL_TRY(hipMemcpyAsync(d.sig.p, sig, n * 64, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.msg.p, msg, n * 32, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.len.p, key_index, n * 4, hipMemcpyHostToDevice, d.stream));
-    STL_RC(keyset_launch(d, *ks, static_cast<const uint32_t*>(d.len.p), static_cast<const uint8_t*>(d.sig.p),
-                         static_cast<const uint8_t*>(d.msg.p), n, static_cast<uint64_t*>(d.bitmap.p), flags, d.stream));
-    STL_TRY(hipMemcpyAsync(host_words.data(), d.bitmap.p, words * 8, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write host_words
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  std::memcpy(accept_bitmap, host_words.data(), (n + 7) / 8);
-  return span.finish(STL_OK);
-}
-
-int stl_keyset_lookup_device(stl_keyset* ks, const uint8_t* d_pk, size_t n, uint32_t* d_key_index,
-                             uint32_t* d_miss_count, void* stream) {
-  if (!ks) return STL_EINVAL;
-  if (n > 0xffffffc0ull || (n && (!d_pk || !d_key_index))) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d_miss_count) STL_TRY(hipMemsetAsync(d_miss_count, 0, 4, s));
-  if (n == 0) return STL_OK;
-  STL_TRY(stl::launch_keyset_lookup(d_pk, (uint32_t)n, ks->d_map(), ks->d_rec(), d_key_index, nullptr, d_miss_count,
-                                    s));
-  return STL_OK;
-}
-
-int stl_keyset_verify_by_key_device(stl_keyset* ks, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_msg,
-                                    size_t n, uint64_t* d_bitmap_words, uint32_t flags, void* stream,
-                                    size_t* misses) {
-  if (misses) *misses = 0;
-  if (!ks) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull || (n && (!d_pk || !d_sig || !d_msg || !d_bitmap_words))) return STL_EINVAL;
-  std::unique_lock<std::mutex> kl(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  if (n == 0) return STL_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ByKeyLease use(stream_ctx(*d, s), s);
-  return keyset_by_key(kl, *d, *ks, use, d_pk, d_sig, d_msg, n, d_bitmap_words, flags, s, misses);
-}
-
-int stl_keyset_signed_blob_verify_batch_device(stl_keyset* ks, uint32_t kind, const uint8_t* d_blobs,
-                                               const uint64_t* d_offset, const uint32_t* d_len, size_t n,
-                                               uint64_t* d_bitmap_words, uint8_t* d_status, uint8_t* d_id,
-                                               uint32_t flags, void* stream, size_t* misses) {
-  if (misses) *misses = 0;
-  if (!ks) return STL_EINVAL;
-  if (kind != STL_BLOB_TRANSACTION && kind != STL_BLOB_VALIDATION) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull || (n && (!d_blobs || !d_offset || !d_len || !d_bitmap_words || !d_status)))
-    return STL_EINVAL;
-  std::unique_lock<std::mutex> kl(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  if (n == 0) return STL_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ByKeyLease use(stream_ctx(*d, s), s);
-  STL_RC(use.b.blob.ensure(n * 128));  // signing hashes, then signatures, then keys
-  uint8_t* msg = static_cast<uint8_t*>(use.b.blob.p);
-  uint8_t* sig = msg + 32 * n;
-  uint8_t* pk = msg + 96 * n;
-  {
-    // the pass of stl_signed_blob_prepare_device; the context's queue under
-    // its mutex until the kernel using it is enqueued
-    std::lock_guard<std::mutex> cl(use.c->mu);
-    uint32_t* ctr = nullptr;
-    STL_RC(ctx_queue(*use.c, n, &ctr, true));
-    STL_TRY(stl::launch_tx_blob(d_blobs, d_offset, d_len, (uint32_t)n, msg, sig, pk, d_id, d_status, ctr,
-                                hash_grid(*d), s, kind));
-  }
-  return keyset_by_key(kl, *d, *ks, use, pk, sig, msg, n, d_bitmap_words, flags, s, misses);
-}
-
-int stl_keyset_verify_by_key(stl_keyset* ks, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, size_t n,
-                             uint8_t* accept_bitmap, uint32_t flags) {
-  if (!ks) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));
-  if (n > 0xffffffc0ull || (n && (!pk || !sig || !msg || !accept_bitmap))) return STL_EINVAL;
-  std::unique_lock<std::mutex> kl(g_ks_mu);
-  Device* dp = nullptr;
-  STL_RC(keyset_for_call(ks, &dp));
-  if (n == 0) return STL_OK;
-  CallSpan span{"stl_keyset_verify_by_key", n};
-  Device& d = *dp;
-  std::lock_guard<std::mutex> dl(d.mu);
-  const size_t words = (n + 63) / 64;
-  std::vector<uint64_t> host_words(words);
-  auto go = [&]() -> int {
-    STL_RC(d.sig.ensure(n * 64));
-    STL_RC(d.msg.ensure(n * 32));
-    STL_RC(d.pk.ensure(n * 32));
-    STL_RC(d.bitmap.ensure(words * 8));
-    STL_TRY(hipMemcpyAsync(d.sig.p, sig, n * 64, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.msg.p, msg, n * 32, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.pk.p, pk, n * 32, hipMemcpyHostToDevice, d.stream));
-    {
-      ByKeyLease use(stream_ctx(d, d.stream), d.stream);
-      STL_RC(keyset_by_key(kl, d, *ks, use, static_cast<const uint8_t*>(d.pk.p), static_cast<const uint8_t*>(d.sig.p),
-                           static_cast<const uint8_t*>(d.msg.p), n, static_cast<uint64_t*>(d.bitmap.p), flags,
-                           d.stream, nullptr));
-    }
-    STL_TRY(hipMemcpyAsync(host_words.data(), d.bitmap.p, words * 8, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write host_words
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  std::memcpy(accept_bitmap, host_words.data(), (n + 7) / 8);
-  return span.finish(STL_OK);
-}
-
-int stl_debug_keyset_rows(const stl_keyset* ks, uint32_t key, uint32_t first_row, uint32_t nrows,
-                          uint32_t* out_words) {
-  if (!out_words) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ks_mu);
-  Device* d = nullptr;
-  STL_RC(keyset_for_call(ks, &d));
-  const stl::KeysetGeometry g = stl::keyset_geometry();
-  const uint64_t rows = (uint64_t)g.windows * g.rows_per_window;
-  if (key == STL_KEYSET_BASE) key = ks->nkeys;
-  else if (key >= ks->nkeys) return STL_EINVAL;
-  if ((uint64_t)first_row + nrows > rows) return STL_EINVAL;
-  if (nrows == 0) return STL_OK;
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(ks->d_tables()) +
-                       ((size_t)key * rows + first_row) * g.row_bytes;
-  STL_TRY(hipDeviceSynchronize());
-  STL_TRY(hipMemcpy(out_words, src, (size_t)nrows * g.row_bytes, hipMemcpyDeviceToHost));
-  return STL_OK;
-}
-
-// ---- signer authority: account IDs and the master-key match (stl_signer.hip) ----
-
-int stl_account_id_batch_device(const uint8_t* d_pk, size_t n, uint8_t* d_account_id, void* stream) {
-  if (n == 0) return STL_OK;
-  if (!d_pk || !d_account_id || n > 0xffffffc0ull) return STL_EINVAL;
-  // the kernel's 16-byte loads and dword stores: refused, never attempted
-  if (((uintptr_t)d_pk & 15u) != 0 || ((uintptr_t)d_account_id & 3u) != 0) return STL_EINVAL;
-  Device* d = nullptr;
-  STL_RC(device_for_call(&d));
-  STL_TRY(stl::launch_account_id(d_pk, (uint32_t)n, d_account_id, static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_tx_blob_signer_batch_device(const uint8_t* d_blobs, const uint64_t* d_offset, const uint32_t* d_len, size_t n,
-                                    uint8_t* d_signer_id, uint8_t* d_account, uint8_t* d_authority, void* stream) {
-  if (n == 0) return STL_OK;
-  if (!d_blobs || !d_offset || !d_len || !d_signer_id || !d_authority || n > 0xffffffc0ull) return STL_EINVAL;
-  if (((uintptr_t)d_signer_id & 3u) != 0 || ((uintptr_t)d_account & 3u) != 0) return STL_EINVAL;
-  Device* d = nullptr;
-  STL_RC(device_for_call(&d));
-  STL_TRY(stl::launch_tx_signer(d_blobs, d_offset, d_len, (uint32_t)n, d_signer_id, d_account, d_authority,
-                                static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_account_id_batch(const uint8_t* pk, size_t n, uint8_t* account_id) {
-  if (n == 0) return STL_OK;
-  if (!pk || !account_id || n > 0xffffffc0ull) return STL_EINVAL;
-  STL_RC(ensure_init());
-  if (g_devs.empty()) return STL_ENODEV;
-  CallSpan span{"stl_account_id_batch", n};
-  DeviceGuard guard;
-  Device& d = *g_devs[0];
-  std::lock_guard<std::mutex> dl(d.mu);
-  std::vector<uint8_t> host(n * STL_ACCOUNT_ID_BYTES);
-  auto go = [&]() -> int {
-    STL_TRY(hipSetDevice(d.ordinal));
-    STL_RC(d.pk.ensure(n * 32));
-    STL_RC(d.msg.ensure(n * STL_ACCOUNT_ID_BYTES));
-    STL_TRY(hipMemcpyAsync(d.pk.p, pk, n * 32, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(stl::launch_account_id(static_cast<const uint8_t*>(d.pk.p), (uint32_t)n, static_cast<uint8_t*>(d.msg.p),
-                                   d.stream));
-    STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, host.size(), hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write host
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  std::memcpy(account_id, host.data(), host.size());
-  return span.finish(STL_OK);
-}
-
-int stl_tx_blob_signer_batch(const uint8_t* blobs, const uint64_t* offset, const uint32_t* len, size_t n,
-                             uint8_t* signer_id, uint8_t* account, uint8_t* authority) {
-  if (n == 0) return STL_OK;
-  if (!blobs || !offset || !len || !signer_id || !authority || n > 0xffffffc0ull) return STL_EINVAL;
-  STL_RC(ensure_init());
-  if (g_devs.empty()) return STL_ENODEV;
-  CallSpan span{"stl_tx_blob_signer_batch", n};
-  DeviceGuard guard;
-  Device& d = *g_devs[0];
-  std::lock_guard<std::mutex> dl(d.mu);
-  std::vector<uint64_t> roff, row_end;
-  uint64_t base = 0, bytes = 0;
-  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
-  const size_t idb = n * STL_ACCOUNT_ID_BYTES;
-  std::vector<uint8_t> host(2 * idb + n);  // signer IDs, accounts, authority
-  auto go = [&]() -> int {
-    STL_TRY(hipSetDevice(d.ordinal));
-    STL_RC(d.pre.ensure(bytes + 16));
-    STL_RC(d.off.ensure(n * 8));
-    STL_RC(d.len.ensure(n * 4));
-    STL_RC(d.msg.ensure(idb));
-    STL_RC(d.txid.ensure(idb));
-    STL_RC(d.status.ensure(n));
-    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(stl::launch_tx_signer(static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
-                                  static_cast<const uint32_t*>(d.len.p), (uint32_t)n, static_cast<uint8_t*>(d.msg.p),
-                                  account ? static_cast<uint8_t*>(d.txid.p) : nullptr,
-                                  static_cast<uint8_t*>(d.status.p), d.stream));
-    STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, idb, hipMemcpyDeviceToHost, d.stream));
-    if (account) STL_TRY(hipMemcpyAsync(host.data() + idb, d.txid.p, idb, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipMemcpyAsync(host.data() + 2 * idb, d.status.p, n, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write host
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  std::memcpy(signer_id, host.data(), idb);
-  if (account) std::memcpy(account, host.data() + idb, idb);
-  std::memcpy(authority, host.data() + 2 * idb, n);
-  return span.finish(STL_OK);
-}
-
-}  // extern "C"
-
-// ---- verified-ID cache: rows already accepted skip the verify (stl_sigcache.hip) ----
-// One cache: on one device the lines (stl_sigcache_core.h), and what it is
-// bound to -- the blob kind and the accept predicate of the rows it may hold.
-struct stl_sigcache {
-  int ordinal = -1;
-  uint32_t sets_log2 = 0, kind = 0, predicate = 0;
-  uint64_t seed = 0;
-  DevBuf lines;
-  stl::SigCacheDev dev() const {
-    return stl::SigCacheDev{static_cast<uint32_t*>(lines.p), (1u << sets_log2) - 1u, seed};
-  }
-};
-
-namespace {
-// The live caches; g_sc_mu as g_ks_mu for the keysets: held while a call looks
-// its handle up and enqueues kernels that touch the lines, and while a cache
-// is destroyed.  Lock order: g_sc_mu before a device's mu / a context's mu.
-std::mutex g_sc_mu;
-std::set<const stl_sigcache*> g_sigcaches;
-
-void sigcache_free_locked(stl_sigcache* c) {
-  g_sigcaches.erase(c);
-  DeviceGuard guard;
-  if (hipSetDevice(c->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
-  c->lines.release();
-  delete c;
-}
-
-void sigcaches_release_all() {
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  while (!g_sigcaches.empty()) sigcache_free_locked(const_cast<stl_sigcache*>(*g_sigcaches.begin()));
-}
-
-// The live cache of a handle on the calling thread's device (g_sc_mu held),
-// by acctdir_for_call's rule; without a device STL_ENODEV comes first.
-int sigcache_for_call(const stl_sigcache* c, Device** d) {
-  STL_RC(device_for_call(d));
-  if (!c || !g_sigcaches.count(c)) return STL_EINVAL;
-  return (*d)->ordinal == c->ordinal ? STL_OK : STL_EINVAL;
-}
-
-// The cached blob verify of n rows on stream s (kl: g_sc_mu, held; c live on
-// d).  The blob pass into the lease's buffers, the probe with the miss list,
-// both counts copied to the lease's host-mapped words behind an event; then
-// the one wait -- for that event, with g_sc_mu released -- and the rows that
-// missed go through run_verify, compacted, their bits ORed into the bitmap
-// the probe wrote.  The insert comes last, under g_sc_mu again (the handle
-// looked up anew: the lines must still be there; `hold`: the host form, which
-// also holds its device's mutex, keeps g_sc_mu throughout instead, by the
-// lock order), and only after every
-// earlier step was enqueued without an error: the compact bitmap it reads is
-// then written in full by this call's verify, so a failed call leaves inserts
-// out but never adds an ID whose verify did not run.
-int sigcache_verify(std::unique_lock<std::mutex>& kl, Device& d, const stl_sigcache* c, ByKeyLease& use,
-                    const uint8_t* d_blobs, const uint64_t* d_offset, const uint32_t* d_len, size_t n,
-                    uint64_t* d_words, uint8_t* d_status, uint8_t* d_id, uint32_t flags, hipStream_t s,
-                    size_t* hits, size_t* verified, bool hold = false) {
-  ByKeyBufs& b = use.b;
-  const stl::SigCacheDev cd = c->dev();
-  const uint32_t kind = c->kind;
-  // signing hashes, signatures, keys; then the IDs when the caller takes none
-  STL_RC(b.blob.ensure(n * (d_id ? 128 : 160)));
-  uint8_t* msg = static_cast<uint8_t*>(b.blob.p);
-  uint8_t* sig = msg + 32 * n;
-  uint8_t* pk = msg + 96 * n;
-  uint8_t* ids = d_id ? d_id : msg + 128 * n;
-  {
-    // the pass of stl_signed_blob_prepare_device; the context's queue under
-    // its mutex until the kernel using it is enqueued
-    std::lock_guard<std::mutex> cl(use.c->mu);
-    uint32_t* ctr = nullptr;
-    STL_RC(ctx_queue(*use.c, n, &ctr, true));
-    STL_TRY(stl::launch_tx_blob(d_blobs, d_offset, d_len, (uint32_t)n, msg, sig, pk, ids, d_status, ctr,
-                                hash_grid(d), s, kind));
-  }
-  STL_RC(b.idx.ensure(256 + align256(n * 4)));
-  if (!b.count) {
-    void* p = nullptr;
-    STL_TRY(hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    b.count = static_cast<uint32_t*>(p);
-  }
-  if (!b.counted) STL_TRY(hipEventCreateWithFlags(&b.counted, hipEventDisableTiming));
-  uint8_t* base = static_cast<uint8_t*>(b.idx.p);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(base);  // [0] misses, [1] hits
-  uint32_t* miss_rows = reinterpret_cast<uint32_t*>(base + 256);
-  STL_TRY(hipMemsetAsync(cnt, 0, 8, s));
-  STL_TRY(stl::launch_sigcache_probe(cd, ids, d_status, (uint32_t)n, d_words, miss_rows, cnt, dev_counters(d), s));
-  STL_TRY(hipMemcpyAsync(b.count, cnt, 8, hipMemcpyDeviceToHost, s));
-  STL_TRY(hipEventRecord(b.counted, s));
-  if (!hold) kl.unlock();
-  // the call's one host wait: the per-signature kernels are sized by the miss count
-  STL_TRY(hipEventSynchronize(b.counted));
-  const size_t m = __atomic_load_n(&b.count[0], __ATOMIC_ACQUIRE);
-  const size_t h = __atomic_load_n(&b.count[1], __ATOMIC_ACQUIRE);
-  if (m + h > n) return STL_EHIP;
-  if (hits) *hits = h;
-  if (verified) *verified = m;
-  if (m == 0) return STL_OK;  // every decidable row a hit: no per-signature kernel
-  const size_t csig = 0, cmsg = align256(m * 64), cpk = cmsg + align256(m * 32), cwords = cpk + align256(m * 32);
-  STL_RC(b.rows.ensure(cwords + (m + 63) / 64 * 8));
-  uint8_t* r = static_cast<uint8_t*>(b.rows.p);
-  STL_TRY(stl::launch_keyset_gather_rows(miss_rows, (uint32_t)m, sig, msg, pk, r + csig, r + cmsg, r + cpk, s));
-  // the mode the flags give and the stream's automatic dedup, sampled on the
-  // compact keys, as the by-key call runs its misses
-  uint32_t mode = stl::kernel_mode(flags);
-  uint32_t* flag_dev = nullptr;
-  STL_RC(auto_dedup_device(*use.c, flags, &mode, &flag_dev));
-  STL_RC(run_verify(d, s, r + csig, r + cmsg, r + cpk, m, reinterpret_cast<uint64_t*>(r + cwords), mode, false,
-                    g_tune_streams.load()));
-  if (flag_dev) STL_TRY(stl::launch_key_sample(r + cpk, (uint32_t)m, flag_dev, s));
-  STL_TRY(stl::launch_keyset_scatter_bits(miss_rows, (uint32_t)m, reinterpret_cast<const uint64_t*>(r + cwords),
-                                          d_words, s));
-  if (!hold) kl.lock();
-  if (!g_sigcaches.count(c)) return STL_OK;  // destroyed during the wait: the outputs stand, nothing to insert into
-  STL_TRY(stl::launch_sigcache_insert(cd, miss_rows, (uint32_t)m, reinterpret_cast<const uint64_t*>(r + cwords), ids,
-                                      s));
-  return STL_OK;
-}
-
-int check_sigcache_rows(const void* blobs, const void* offset, const void* len, size_t n, const void* bitmap,
-                        const void* status, const void* id, uint32_t flags) {
-  if (n > 0xffffffc0ull || (n && (!blobs || !offset || !len || !bitmap || !status))) return STL_EINVAL;
-  if (((uintptr_t)id & 15u) != 0) return STL_EINVAL;
-  return check_flags(flags);
-}
-}  // namespace
-
-extern "C" {
-
-int stl_sigcache_create(uint32_t sets_log2, uint32_t kind, uint32_t flags, uint64_t seed, stl_sigcache** out) {
-  if (out) *out = nullptr;
-  if (!out || sets_log2 > STL_SIGCACHE_MAX_SETS_LOG2) return STL_EINVAL;
-  if (kind != STL_BLOB_TRANSACTION && kind != STL_BLOB_VALIDATION) return STL_EINVAL;
-  STL_RC(check_keyset_flags(flags));  // the predicate bits; no execution flag belongs to a cache
-  Device* d = nullptr;
-  STL_RC(device_for_call(&d));
-  while (seed == 0) {
-    std::random_device rd;
-    seed = ((uint64_t)rd() << 32) ^ rd();
-  }
-  std::unique_ptr<stl_sigcache> c(new stl_sigcache());
-  c->ordinal = d->ordinal;
-  c->sets_log2 = sets_log2;
-  c->kind = kind;
-  c->predicate = stl::sigcache_predicate(flags);
-  c->seed = seed;
-  const size_t bytes = stl::sigcache_bytes(sets_log2);
-  DeviceGuard guard;
-  auto go = [&]() -> int {
-    std::lock_guard<std::mutex> lk(d->mu);
-    STL_TRY(hipSetDevice(d->ordinal));
-    STL_RC(c->lines.ensure(bytes));
-    STL_TRY(hipMemsetAsync(c->lines.p, 0, bytes, d->stream));
-    STL_TRY(hipStreamSynchronize(d->stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {
-    (void)hipStreamSynchronize(d->stream);
-    c->lines.release();
-    return rc;
-  }
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  g_sigcaches.insert(c.get());
-  *out = c.release();
-  return STL_OK;
-}
-
-void stl_sigcache_destroy(stl_sigcache* c) {
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  if (c && g_sigcaches.count(c)) sigcache_free_locked(c);
-}
-
-int stl_sigcache_get_info(const stl_sigcache* c, stl_sigcache_info* out) {
-  if (!out || out->struct_size != sizeof(stl_sigcache_info)) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  if (!c || !g_sigcaches.count(c)) return STL_EINVAL;
-  out->sets_log2 = c->sets_log2;
-  out->ways = STL_SIGCACHE_WAYS;
-  out->kind = c->kind;
-  out->predicate = c->predicate;
-  out->device = c->ordinal;
-  out->bytes = stl::sigcache_bytes(c->sets_log2);
-  out->seed = c->seed;
-  return STL_OK;
-}
-
-int stl_sigcache_clear(stl_sigcache* c, void* stream) {
-  if (!c) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  Device* d = nullptr;
-  STL_RC(sigcache_for_call(c, &d));
-  STL_TRY(hipMemsetAsync(c->lines.p, 0, stl::sigcache_bytes(c->sets_log2), static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_sigcache_lookup_device(stl_sigcache* c, const uint8_t* d_id, size_t n, uint64_t* d_hit_words, void* stream) {
-  if (!c) return STL_EINVAL;
-  if (n > 0xffffffc0ull || (n && (!d_id || !d_hit_words)) || ((uintptr_t)d_id & 15u) != 0) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_sc_mu);
-  Device* d = nullptr;
-  STL_RC(sigcache_for_call(c, &d));
-  if (n == 0) return STL_OK;
-  STL_TRY(stl::launch_sigcache_lookup(c->dev(), d_id, (uint32_t)n, d_hit_words, static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_sigcache_signed_blob_verify_batch_device(stl_sigcache* c, const uint8_t* d_blobs, const uint64_t* d_offset,
-                                                 const uint32_t* d_len, size_t n, uint64_t* d_bitmap_words,
-                                                 uint8_t* d_status, uint8_t* d_id, uint32_t flags, void* stream,
-                                                 size_t* hits, size_t* verified) {
-  if (hits) *hits = 0;
-  if (verified) *verified = 0;
-  if (!c) return STL_EINVAL;
-  STL_RC(check_sigcache_rows(d_blobs, d_offset, d_len, n, d_bitmap_words, d_status, d_id, flags));
-  std::unique_lock<std::mutex> kl(g_sc_mu);
-  Device* d = nullptr;
-  STL_RC(sigcache_for_call(c, &d));
-  if (stl::sigcache_predicate(flags) != c->predicate) return STL_EINVAL;
-  if (n == 0) return STL_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ByKeyLease use(stream_ctx(*d, s), s);
-  return sigcache_verify(kl, *d, c, use, d_blobs, d_offset, d_len, n, d_bitmap_words, d_status, d_id, flags, s, hits,
-                         verified);
-}
-
-int stl_sigcache_signed_blob_verify_batch(stl_sigcache* c, const uint8_t* blobs, const uint64_t* offset,
-                                          const uint32_t* len, size_t n, uint8_t* accept_bitmap, uint8_t* status,
-                                          uint8_t* id, uint32_t flags, size_t* hits, size_t* verified) {
-  if (hits) *hits = 0;
-  if (verified) *verified = 0;
-  if (!c) return STL_EINVAL;
-  STL_RC(check_sigcache_rows(blobs, offset, len, n, accept_bitmap, status, nullptr, flags));
-  std::unique_lock<std::mutex> kl(g_sc_mu);
-  Device* dp = nullptr;
-  STL_RC(sigcache_for_call(c, &dp));
-  if (stl::sigcache_predicate(flags) != c->predicate) return STL_EINVAL;
-  if (n == 0) return STL_OK;
-  Device& d = *dp;
-  CallSpan span{"stl_sigcache_signed_blob_verify_batch", n};
-  DeviceGuard guard;
-  std::lock_guard<std::mutex> dl(d.mu);
-  std::vector<uint64_t> roff, row_end;
-  uint64_t base = 0, bytes = 0;
-  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
-  const size_t words = (n + 63) / 64;
-  std::vector<uint64_t> host_words(words);
-  std::vector<uint8_t> host(n + (id ? 32 * n : 0));  // status, then the IDs
-  auto go = [&]() -> int {
-    STL_TRY(hipSetDevice(d.ordinal));
-    STL_RC(d.pre.ensure(bytes + 16));
-    STL_RC(d.off.ensure(n * 8));
-    STL_RC(d.len.ensure(n * 4));
-    STL_RC(d.bitmap.ensure(words * 8));
-    STL_RC(d.status.ensure(n));
-    if (id) STL_RC(d.txid.ensure(n * 32));
-    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
-    if (id) STL_TRY(hipMemsetAsync(d.txid.p, 0, n * 32, d.stream));  // a malformed row's ID is not written
-    {
-      ByKeyLease use(stream_ctx(d, d.stream), d.stream);
-      STL_RC(sigcache_verify(kl, d, c, use, static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
-                             static_cast<const uint32_t*>(d.len.p), n, static_cast<uint64_t*>(d.bitmap.p),
-                             static_cast<uint8_t*>(d.status.p), id ? static_cast<uint8_t*>(d.txid.p) : nullptr, flags,
-                             d.stream, hits, verified, true));
-    }
-    STL_TRY(hipMemcpyAsync(host_words.data(), d.bitmap.p, words * 8, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipMemcpyAsync(host.data(), d.status.p, n, hipMemcpyDeviceToHost, d.stream));
-    if (id) STL_TRY(hipMemcpyAsync(host.data() + n, d.txid.p, 32 * n, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write the host buffers
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  std::memcpy(accept_bitmap, host_words.data(), (n + 7) / 8);
-  std::memcpy(status, host.data(), n);
-  if (id) std::memcpy(id, host.data() + n, 32 * n);
-  return span.finish(STL_OK);
-}
-
-}  // extern "C"
-
-// ---- account directory: Transactor::checkSig's verdict per row (stl_acctdir.hip) ----
-// One directory: on one device the slots, the records and two words of
-// bookkeeping (stl_acctdir.h AcctDirDev), plus the staging buffer of upsert.
-// The record count is the device's word; `records` is the host's copy, read
-// back at the end of every upsert (count_stale: that read has yet to succeed).
-struct stl_acctdir {
-  int ordinal = -1;
-  uint32_t capacity = 0, nslots = 0;
-  uint64_t seed = 0;
-  uint32_t records = 0, longest_probe = 0;
-  bool count_stale = false;
-  DevBuf slots, recs, meta, stage;
-  stl::AcctDirDev dev() const {
-    return stl::AcctDirDev{static_cast<uint32_t*>(slots.p), static_cast<uint32_t*>(recs.p),
-                           static_cast<uint32_t*>(meta.p), nslots - 1, capacity, seed};
-  }
-  size_t bytes() const { return (size_t)nslots * 4 + (size_t)capacity * stl::kAdRecWords * 4; }
-};
-
-namespace {
-// The live directories; g_ad_mu as g_ks_mu for the keysets: held while a call
-// looks its handle up and enqueues its kernels, and while one is destroyed.
-// Lock order: g_ad_mu before a device's mu.
-std::mutex g_ad_mu;
-std::set<const stl_acctdir*> g_acctdirs;
-
-void acctdir_free_locked(stl_acctdir* dir) {
-  g_acctdirs.erase(dir);
-  DeviceGuard guard;
-  if (hipSetDevice(dir->ordinal) == hipSuccess) (void)hipDeviceSynchronize();
-  dir->slots.release();
-  dir->recs.release();
-  dir->meta.release();
-  dir->stage.release();
-  delete dir;
-}
-
-void acctdirs_release_all() {
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  while (!g_acctdirs.empty()) acctdir_free_locked(const_cast<stl_acctdir*>(*g_acctdirs.begin()));
-}
-
-// The live directory of a handle on the calling thread's device (g_ad_mu
-// held), by keyset_for_call's rule; without a device STL_ENODEV comes first.
-int acctdir_for_call(const stl_acctdir* dir, Device** d) {
-  STL_RC(device_for_call(d));
-  if (!dir || !g_acctdirs.count(dir)) return STL_EINVAL;
-  return (*d)->ordinal == dir->ordinal ? STL_OK : STL_EINVAL;
-}
-
-// meta[0 .. 2) -> the host's copy.  Not counted by the fault injection: it
-// also runs on upsert's failure path.
-bool acctdir_read_meta(stl_acctdir& dir) {
-  uint32_t m[2] = {0, 0};
-  if (hipMemcpy(m, dir.meta.p, sizeof(m), hipMemcpyDeviceToHost) != hipSuccess) {
-    dir.count_stale = true;
-    return false;
-  }
-  dir.records = std::min(m[0], dir.capacity);
-  dir.longest_probe = m[1];
-  dir.count_stale = false;
-  return true;
-}
-}  // namespace
-
-extern "C" {
-
-int stl_acctdir_create(uint32_t capacity, uint64_t seed, stl_acctdir** out) {
-  if (out) *out = nullptr;
-  if (!out || capacity == 0 || capacity > STL_ACCTDIR_MAX_ACCOUNTS) return STL_EINVAL;
-  Device* d = nullptr;
-  STL_RC(device_for_call(&d));
-  while (seed == 0) {
-    std::random_device rd;
-    seed = ((uint64_t)rd() << 32) ^ rd();
-  }
-  std::unique_ptr<stl_acctdir> dir(new stl_acctdir());
-  dir->ordinal = d->ordinal;
-  dir->capacity = capacity;
-  dir->nslots = stl::acctdir_slots(capacity);
-  dir->seed = seed;
-  DeviceGuard guard;
-  auto go = [&]() -> int {
-    std::lock_guard<std::mutex> lk(d->mu);
-    STL_TRY(hipSetDevice(d->ordinal));
-    STL_RC(dir->slots.ensure((size_t)dir->nslots * 4));
-    STL_RC(dir->recs.ensure((size_t)capacity * stl::kAdRecWords * 4));
-    STL_RC(dir->meta.ensure(8));
-    STL_TRY(hipMemsetAsync(dir->slots.p, 0xFF, (size_t)dir->nslots * 4, d->stream));
-    STL_TRY(hipMemsetAsync(dir->recs.p, 0, (size_t)capacity * stl::kAdRecWords * 4, d->stream));
-    STL_TRY(hipMemsetAsync(dir->meta.p, 0, 8, d->stream));
-    STL_TRY(hipStreamSynchronize(d->stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {
-    (void)hipStreamSynchronize(d->stream);
-    dir->slots.release();
-    dir->recs.release();
-    dir->meta.release();
-    return rc;
-  }
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  g_acctdirs.insert(dir.get());
-  *out = dir.release();
-  return STL_OK;
-}
-
-void stl_acctdir_destroy(stl_acctdir* dir) {
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  if (dir && g_acctdirs.count(dir)) acctdir_free_locked(dir);
-}
-
-int stl_acctdir_get_info(const stl_acctdir* dir, stl_acctdir_info* out) {
-  if (!out || out->struct_size != sizeof(stl_acctdir_info)) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  if (!dir || !g_acctdirs.count(dir)) return STL_EINVAL;
-  if (dir->count_stale) {
-    DeviceGuard guard;
-    if (hipSetDevice(dir->ordinal) != hipSuccess || !acctdir_read_meta(*const_cast<stl_acctdir*>(dir))) return STL_EHIP;
-  }
-  out->capacity = dir->capacity;
-  out->records = dir->records;
-  out->slots = dir->nslots;
-  out->longest_probe = dir->longest_probe;
-  out->device = dir->ordinal;
-  out->bytes = dir->bytes();
-  out->seed = dir->seed;
-  return STL_OK;
-}
-
-int stl_acctdir_upsert(stl_acctdir* dir, const uint8_t* account_id, const uint8_t* flags, const uint8_t* regular_key,
-                       size_t m) {
-  if (m == 0) return STL_OK;
-  if (!dir || !account_id || !flags || m > 0xffffffc0ull) return STL_EINVAL;
-  std::vector<uint32_t> staged;
-  if (!stl::acctdir_stage(account_id, flags, regular_key, m, staged)) return STL_EINVAL;
-  const size_t distinct = staged.size() / stl::kAdRecWords;
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  Device* d = nullptr;
-  STL_RC(acctdir_for_call(dir, &d));
-  DeviceGuard guard;
-  std::lock_guard<std::mutex> dl(d->mu);
-  if (dir->count_stale && !acctdir_read_meta(*dir)) return STL_EHIP;
-  if ((size_t)dir->records + distinct > dir->capacity) return STL_ENOMEM;  // before any device work
-  const size_t rec_bytes = distinct * stl::kAdRecWords * 4;
-  auto go = [&]() -> int {
-    STL_TRY(hipSetDevice(d->ordinal));
-    STL_RC(dir->stage.ensure(rec_bytes + distinct * 4));
-    uint32_t* d_staged = static_cast<uint32_t*>(dir->stage.p);
-    uint32_t* d_new = d_staged + distinct * stl::kAdRecWords;
-    STL_TRY(hipMemcpyAsync(d_staged, staged.data(), rec_bytes, hipMemcpyHostToDevice, d->stream));
-    STL_TRY(stl::launch_acctdir_find(dir->dev(), d_staged, (uint32_t)distinct, d_new, d->stream));
-    STL_TRY(stl::launch_acctdir_claim(dir->dev(), d_staged, (uint32_t)distinct, d_new, d->stream));
-    STL_TRY(hipStreamSynchronize(d->stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) (void)hipStreamSynchronize(d->stream);  // nothing may still read `staged`
-  const bool read = acctdir_read_meta(*dir);       // the count moved even where the call failed
-  return rc ? rc : (read ? STL_OK : STL_EHIP);
-}
-
-int stl_acctdir_lookup_device(stl_acctdir* dir, const uint8_t* d_account_id, size_t n, uint8_t* d_flags,
-                              uint8_t* d_regular_key, void* stream) {
-  if (n == 0) return STL_OK;
-  if (!dir || !d_account_id || !d_flags || n > 0xffffffc0ull) return STL_EINVAL;
-  if (((uintptr_t)d_account_id & 3u) != 0 || ((uintptr_t)d_regular_key & 3u) != 0) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  Device* d = nullptr;
-  STL_RC(acctdir_for_call(dir, &d));
-  STL_TRY(stl::launch_acctdir_lookup(dir->dev(), d_account_id, (uint32_t)n, d_flags, d_regular_key,
-                                     static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_acctdir_tx_blob_authority_device(stl_acctdir* dir, const uint8_t* d_blobs, const uint64_t* d_offset,
-                                         const uint32_t* d_len, size_t n, uint8_t* d_signer_id, uint8_t* d_account,
-                                         uint8_t* d_authority, void* stream) {
-  if (n == 0) return STL_OK;
-  if (!dir || !d_blobs || !d_offset || !d_len || !d_authority || n > 0xffffffc0ull) return STL_EINVAL;
-  if (((uintptr_t)d_signer_id & 3u) != 0 || ((uintptr_t)d_account & 3u) != 0) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  Device* d = nullptr;
-  STL_RC(acctdir_for_call(dir, &d));
-  STL_TRY(stl::launch_acctdir_authority(dir->dev(), d_blobs, d_offset, d_len, (uint32_t)n, d_signer_id, d_account,
-                                        d_authority, static_cast<hipStream_t>(stream)));
-  return STL_OK;
-}
-
-int stl_acctdir_tx_blob_authority(stl_acctdir* dir, const uint8_t* blobs, const uint64_t* offset, const uint32_t* len,
-                                  size_t n, uint8_t* signer_id, uint8_t* account, uint8_t* authority) {
-  if (n == 0) return STL_OK;
-  if (!dir || !blobs || !offset || !len || !authority || n > 0xffffffc0ull) return STL_EINVAL;
-  std::lock_guard<std::mutex> lk(g_ad_mu);
-  Device* dp = nullptr;
-  STL_RC(acctdir_for_call(dir, &dp));
-  Device& d = *dp;
-  CallSpan span{"stl_acctdir_tx_blob_authority", n};
-  DeviceGuard guard;
-  std::lock_guard<std::mutex> dl(d.mu);
-  std::vector<uint64_t> roff, row_end;
-  uint64_t base = 0, bytes = 0;
-  rebase(offset, len, 0, n, roff, row_end, &base, &bytes);
-  const size_t idb = n * STL_ACCOUNT_ID_BYTES;
-  std::vector<uint8_t> host(2 * idb + n);  // signer IDs, accounts, authority
-  auto go = [&]() -> int {
-    STL_TRY(hipSetDevice(d.ordinal));
-    STL_RC(d.pre.ensure(bytes + 16));
-    STL_RC(d.off.ensure(n * 8));
-    STL_RC(d.len.ensure(n * 4));
-    STL_RC(d.msg.ensure(idb));
-    STL_RC(d.txid.ensure(idb));
-    STL_RC(d.status.ensure(n));
-    if (bytes) STL_TRY(hipMemcpyAsync(d.pre.p, blobs + base, bytes, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.off.p, roff.data(), n * 8, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(hipMemcpyAsync(d.len.p, len, n * 4, hipMemcpyHostToDevice, d.stream));
-    STL_TRY(stl::launch_acctdir_authority(
-        dir->dev(), static_cast<const uint8_t*>(d.pre.p), static_cast<const uint64_t*>(d.off.p),
-        static_cast<const uint32_t*>(d.len.p), (uint32_t)n, signer_id ? static_cast<uint8_t*>(d.msg.p) : nullptr,
-        account ? static_cast<uint8_t*>(d.txid.p) : nullptr, static_cast<uint8_t*>(d.status.p), d.stream));
-    if (signer_id) STL_TRY(hipMemcpyAsync(host.data(), d.msg.p, idb, hipMemcpyDeviceToHost, d.stream));
-    if (account) STL_TRY(hipMemcpyAsync(host.data() + idb, d.txid.p, idb, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipMemcpyAsync(host.data() + 2 * idb, d.status.p, n, hipMemcpyDeviceToHost, d.stream));
-    STL_TRY(hipStreamSynchronize(d.stream));
-    return STL_OK;
-  };
-  const int rc = go();
-  if (rc) {  // nothing may still read the caller's rows or write host
-    (void)hipStreamSynchronize(d.stream);
-    return span.finish(rc);
-  }
-  if (signer_id) std::memcpy(signer_id, host.data(), idb);
-  if (account) std::memcpy(account, host.data() + idb, idb);
-  std::memcpy(authority, host.data() + 2 * idb, n);
-  return span.finish(STL_OK);
 }
 
 }  // extern "C"

@@ -499,32 +499,16 @@ ACCTDIR_MAX_ACCOUNTS = N.STL_ACCTDIR_MAX_ACCOUNTS
                     N.STL_AUTH_BAD_AUTH_MASTER, N.STL_AUTH_NO_ACCOUNT, N.STL_AUTH_UNDECIDED)
 
 
-class AcctDirInfo(ctypes.Structure):
-    """stl_acctdir_info (include/stl.h)."""
-    _fields_ = [("struct_size", ctypes.c_uint32), ("capacity", ctypes.c_uint32), ("records", ctypes.c_uint32),
-                ("slots", ctypes.c_uint32), ("longest_probe", ctypes.c_uint32), ("device", ctypes.c_int32),
-                ("bytes", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
-
-
-class AccountDirectory:
-    """A device-resident snapshot of the account-root fields Transactor::checkSig
-    reads (stl_acctdir_create), keyed by account ID and updated per ledger with
-    ``upsert``; ``tx_blob_authority_device`` gives checkSig's verdict (AUTH_*)
-    per serialized transaction against the state as last upserted.
-
-        with AccountDirectory(capacity) as d:
-            d.upsert(ids, flags, regular_keys)
-            out = d.tx_blob_authority_device(blobs, offsets, lengths)
-    """
-
-    def __init__(self, capacity, seed=0):
-        h = ctypes.c_void_p()
-        N.check(N.load().stl_acctdir_create(int(capacity), int(seed), ctypes.byref(h)), "stl_acctdir_create")
-        self._h = h
+class _DeviceObject:
+    """A handle object of libstl that lives on one device (``_h``, made by the
+    subclass's constructor): closing, use as a context manager, ``handle`` and
+    ``info`` over ``<_prefix>_destroy`` / ``<_prefix>_get_info``."""
+    _prefix, _Info = None, None
+    _info_skip = ("struct_size",)
 
     def close(self):
         if self._h is not None:
-            N.load().stl_acctdir_destroy(self._h)
+            getattr(N.load(), self._prefix + "_destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -544,9 +528,36 @@ class AccountDirectory:
         return self._h
 
     def info(self):
-        i = AcctDirInfo(struct_size=ctypes.sizeof(AcctDirInfo))
-        N.check(N.load().stl_acctdir_get_info(self._h, ctypes.byref(i)), "stl_acctdir_get_info")
-        return {k: getattr(i, k) for k, _ in AcctDirInfo._fields_ if k != "struct_size"}
+        i = self._Info(struct_size=ctypes.sizeof(self._Info))
+        name = self._prefix + "_get_info"
+        N.check(getattr(N.load(), name)(self._h, ctypes.byref(i)), name)
+        return {k: getattr(i, k) for k, _ in self._Info._fields_ if k not in self._info_skip}
+
+
+class AcctDirInfo(ctypes.Structure):
+    """stl_acctdir_info (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("capacity", ctypes.c_uint32), ("records", ctypes.c_uint32),
+                ("slots", ctypes.c_uint32), ("longest_probe", ctypes.c_uint32), ("device", ctypes.c_int32),
+                ("bytes", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
+
+
+class AccountDirectory(_DeviceObject):
+    """A device-resident snapshot of the account-root fields Transactor::checkSig
+    reads (stl_acctdir_create), keyed by account ID and updated per ledger with
+    ``upsert``; ``tx_blob_authority_device`` gives checkSig's verdict (AUTH_*)
+    per serialized transaction against the state as last upserted.
+
+        with AccountDirectory(capacity) as d:
+            d.upsert(ids, flags, regular_keys)
+            out = d.tx_blob_authority_device(blobs, offsets, lengths)
+    """
+
+    _prefix, _Info = "stl_acctdir", AcctDirInfo
+
+    def __init__(self, capacity, seed=0):
+        h = ctypes.c_void_p()
+        N.check(N.load().stl_acctdir_create(int(capacity), int(seed), ctypes.byref(h)), "stl_acctdir_create")
+        self._h = h
 
     def upsert(self, account_id, flags, regular_key=None):
         """Host arrays: account_id (m, 20) uint8, flags (m,) uint8 of ACCT_*
@@ -644,7 +655,7 @@ class SigCacheInfo(ctypes.Structure):
                 ("bytes", ctypes.c_uint64), ("seed", ctypes.c_uint64)]
 
 
-class SigCache:
+class SigCache(_DeviceObject):
     """A device-resident cache of the IDs of signed objects the verify has
     accepted (stl_sigcache_create), bound to one blob kind and one accept
     predicate (``policy``: the policy bit, N.STL_DEBUG_RAW_PREDICATE).  A row
@@ -656,37 +667,13 @@ class SigCache:
             out = c.signed_blob_verify_batch_device(blobs, offsets, lengths)   # ledger close: all hits
     """
 
+    _prefix, _Info = "stl_sigcache", SigCacheInfo
+
     def __init__(self, sets_log2, kind=BLOB_TRANSACTION, policy=POLICY_SODIUM_1_0_18, seed=0):
         h = ctypes.c_void_p()
         N.check(N.load().stl_sigcache_create(int(sets_log2), int(kind), int(policy), int(seed), ctypes.byref(h)),
                 "stl_sigcache_create")
         self._h = h
-
-    def close(self):
-        if self._h is not None:
-            N.load().stl_sigcache_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def info(self):
-        i = SigCacheInfo(struct_size=ctypes.sizeof(SigCacheInfo))
-        N.check(N.load().stl_sigcache_get_info(self._h, ctypes.byref(i)), "stl_sigcache_get_info")
-        return {k: getattr(i, k) for k, _ in SigCacheInfo._fields_ if k != "struct_size"}
 
     def clear(self, stream=None):
         """Empties the cache: a memset enqueued on ``stream``."""
@@ -777,7 +764,7 @@ class KeysetInfo(ctypes.Structure):
                 ("device", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64)]
 
 
-class Keyset:
+class Keyset(_DeviceObject):
     """A registered signer set (stl_keyset_create): per-key comb tables on the
     current device, verified against by key index -- 64 table additions per
     signature, no doubling, the same bits as the per-signature calls.
@@ -786,37 +773,14 @@ class Keyset:
             words = ks.verify_batch_device(key_index, sig, msg)
     """
 
+    _prefix, _Info = "stl_keyset", KeysetInfo
+    _info_skip = ("struct_size", "reserved")
+
     def __init__(self, pks):
         pks = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 32)
         h = ctypes.c_void_p()
         N.check(N.load().stl_keyset_create(_buf(pks), pks.shape[0], 0, ctypes.byref(h)), "stl_keyset_create")
         self._h = h
-
-    def close(self):
-        if self._h is not None:
-            N.load().stl_keyset_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    @property
-    def handle(self):
-        return self._h
-
-    def info(self):
-        i = KeysetInfo(struct_size=ctypes.sizeof(KeysetInfo))
-        N.check(N.load().stl_keyset_get_info(self._h, ctypes.byref(i)), "stl_keyset_get_info")
-        return {k: getattr(i, k) for k, _ in KeysetInfo._fields_ if k not in ("struct_size", "reserved")}
 
     def find(self, pk):
         """First index of the 32-byte key, or -1."""

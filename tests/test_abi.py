@@ -31,6 +31,20 @@ def test_library_exports_every_declared_symbol():
     assert set(declared_symbols()) == bound
 
 
+def test_library_exports_no_undeclared_stl_symbol():
+    """The converse: every C-linkage ``stl_*`` symbol libstl.so exports is
+    declared in include/stl.h -- a host helper that picked up C linkage (the
+    host files define theirs inside ``extern "C"`` blocks) would show here.
+    The C++ helpers in namespace stl are mangled (_ZN3stl...) and not meant."""
+    import subprocess
+    from stellard_amd import _native
+    out = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], check=True, capture_output=True,
+                         text=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    extra = sorted({s for s in exported if s.startswith("stl_")} - set(declared_symbols()))
+    assert not extra
+
+
 def test_python_constants_match_header():
     """Every numeric STL_* macro of include/stl.h has the same value in
     stellard_amd/_native.py (the ctypes mirror the tests and bench use)."""
