@@ -861,6 +861,49 @@ int stl_sigcache_signed_blob_verify_batch(stl_sigcache *c, const uint8_t *blobs,
                                           const uint32_t *len, size_t n, uint8_t *accept_bitmap, uint8_t *status,
                                           uint8_t *id, uint32_t flags, size_t *hits, size_t *verified);
 
+/* ---- SHAMap root: the hash that names a set ----
+ * Consensus names a transaction set by the root hash of its SHAMap: a proposal's position, the
+ * check of an acquired set (LedgerConsensus.cpp:338), a ledger header's txHash, CanonicalTXSet's
+ * salt (LedgerConsensus.cpp:969).  The shape of the tree is a function of the set of keys
+ * (SHAMap.cpp:680-849: a leaf sits at the shallowest depth where its nibble prefix is unique, under
+ * the root at the least), an inner node hashes as SHA512Half("MIN\0" || 16 child hashes, zeros for
+ * an empty branch) (SHAMapTreeNode.cpp:257-274), and the empty map's root is 32 zero bytes.  So the
+ * root is a function of the keys and their leaf hashes alone.  For a tree without metadata
+ * (tnTRANSACTION_NM) the leaf hash is the key, the transaction ID; for the closed ledger's
+ * transaction tree and the state tree the leaf hashes come from stl_tx_hash_batch_device over the
+ * prefixed leaf preimages.
+ *
+ * d_key: n * 32 bytes; d_leaf_hash: n * 32 bytes, or NULL (the leaf hash is the key: a transaction
+ * set); d_select_words: ceil(n / 64) words in the accept bitmaps' layout, or NULL (all rows): only
+ * rows whose bit is 1 are in the map, so the verify's bitmap can be passed as it is; d_root: 32
+ * bytes; d_counts: 4 x uint32 or NULL: [0] distinct items, [1] selected rows dropped as duplicates
+ * of a key, [2] inner nodes hashed, [3] the deepest inner node's depth.
+ * DUPLICATES: among selected rows with equal keys the lowest row index supplies the leaf hash
+ * (SHAMap::addItem refuses the second).  n == 0, or nothing selected: a zero root, zero counts.
+ * DEFERRED ROWS: the blob calls write a zero ID for a row they defer (STL_TX_DEFERRED), and a
+ * malformed row's ID is not written at all: before d_id of a blob call is passed as d_key, supply
+ * those rows' IDs or clear their select bits -- the accept bitmap does the latter.
+ * Before any device work: a NULL d_root, a NULL d_key with n > 0, n > STL_SHAMAP_MAX_ITEMS, d_key
+ * or d_leaf_hash not 16-byte aligned, d_root or d_counts not 4-byte aligned is STL_EINVAL.  Runs on
+ * the calling thread's current device.  A failure is a negative code; the outputs are written by
+ * the call's last kernel alone, so a call that failed has not written them.
+ * SYNCHRONISATION: none.  The call enqueues a fixed sequence on `stream` -- four 64-bit radix sort
+ * passes (a fifth of one bit with a select bitmap), a scan, 64 level launches of which those
+ * without a node at their depth return at once -- and returns; every count stays on the device.
+ * MEMORY: the stream context holds the workspace, 89 B per row (16 B sort words, 8 B row numbers,
+ * 1 B neighbour byte, 32 B sorted key, 32 B hash slot) plus the sort's temporary storage (what
+ * rocPRIM asks for n rows, whatever the keys: 8 KB at 2^20 rows, 2 MB at 2^24) and 512 B; nothing
+ * is sized by the number of inner nodes, which adversarial keys push to 63 (n - 1) + 1.
+ * With stl_set_phase_timing on, a call's sort, heads-and-neighbours, level and finish times are
+ * added to stl_stats.phase_ns[0..3] as one chunk. */
+#define STL_SHAMAP_MAX_ITEMS 16777216u
+int stl_shamap_root_device(const uint8_t *d_key, const uint8_t *d_leaf_hash, const uint64_t *d_select_words,
+                           size_t n, uint8_t *d_root, uint32_t *d_counts, void *stream);
+/* Host form: host memory (any alignment), synchronous: upload, the device form, 32 + 16 bytes back.
+ * select_bitmap: ceil(n / 8) bytes, bit i of byte i / 8, or NULL; counts: nullable. */
+int stl_shamap_root(const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *select_bitmap, size_t n,
+                    uint8_t root[32], uint32_t counts[4]);
+
 #ifdef __cplusplus
 }
 #endif

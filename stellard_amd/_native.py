@@ -85,6 +85,9 @@ STL_AUTH_UNDECIDED = 6
 STL_SIGCACHE_MAX_SETS_LOG2 = 24
 STL_SIGCACHE_WAYS = 4
 
+# SHAMap root (stl_shamap_root*)
+STL_SHAMAP_MAX_ITEMS = 16777216
+
 # arithmetic self-test (stl_debug_selftest_*; row formats in csrc/stl_selftest.h)
 STL_SELFTEST_OPS = 47
 STL_SELFTEST_GROUP_OPS = 7
@@ -190,6 +193,8 @@ SYMBOLS = [
      [_P, _U8P, _P, _P, ctypes.c_size_t, _P, _U8P, _U8P, ctypes.c_uint32, _P, _P, _P]),
     ("stl_sigcache_signed_blob_verify_batch", ctypes.c_int,
      [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, ctypes.c_uint32, _P, _P]),
+    ("stl_shamap_root_device", ctypes.c_int, [_U8P, _U8P, _P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_root", ctypes.c_int, [_U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -13,6 +13,8 @@
                                  two-step insert and decision function
   tests/native/libhostemu_sigcache.so  the verified-ID cache's hash, probe
                                  and insert
+  tests/native/libhostemu_shamap.so  the SHAMap root's nibble, common prefix,
+                                 node rule and inner-node hash
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -30,15 +32,16 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
-                "stl_selftest.hip",
+                "stl_shamap.hip", "stl_selftest.hip",
                 "stl_api.cpp", "stl_api_keyset.cpp", "stl_api_authority.cpp", "stl_api_sigcache.cpp",
-                "stl_batcher.cpp"]
+                "stl_api_shamap.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
                                "stl_comb.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h",
                                "stl_hash160.h", "stl_signer_core.h", "stl_signer.h",
                                "stl_acctdir_core.h", "stl_acctdir.h",
                                "stl_sigcache_core.h", "stl_sigcache.h",
+                               "stl_shamap_core.h", "stl_shamap.h",
                                "stl_group.h", "stl_selftest.h", "stl_host.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
@@ -73,7 +76,7 @@ def _run(cmd, cwd=ROOT):
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
 HOST_ONLY = ["stl_host.h"]
 HOST_DEPS = HOST_ONLY + ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
-             "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", os.path.join("..", "..", "include", "stl.h")]
+             "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", "stl_shamap.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -137,6 +140,7 @@ SMALL_HARNESSES = {
     "acctdir": ("hostemu_acctdir.cpp", ("stl_acctdir_core.h", "stl_hash160.h", "stl_signer_core.h", "stl_txblob.h",
                                         "stl_sha512.h", "stl_fe25519.h")),
     "sigcache": ("hostemu_sigcache.cpp", ("stl_sigcache_core.h",)),
+    "shamap": ("hostemu_shamap.cpp", ("stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -182,6 +186,10 @@ def build_hostemu_sigcache(force=False):
     return _build_small("sigcache", force)
 
 
+def build_hostemu_shamap(force=False):
+    return _build_small("shamap", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -204,7 +212,8 @@ def main(argv=None):
         jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force),
                 ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force),
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
-                ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force)]
+                ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
+                ex.submit(build_hostemu_shamap, force)]
         for j in jobs:
             j.result()
     build_oracle()

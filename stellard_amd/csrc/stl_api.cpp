@@ -175,9 +175,6 @@ std::unique_ptr<StreamCtx> take_spare(CtxSpares& sp) {
   return z;
 }
 
-// the device's phase clock when timing is on, else none
-const stl::PhaseClock* phase_clock(Device& d) { return g_phase_timing.load() ? &d.clock : nullptr; }
-
 std::mutex g_mu;
 bool g_init = false;
 int g_shards_per_device = 1;
@@ -221,6 +218,9 @@ bool g_trace = false;
 }  // namespace
 
 std::vector<std::unique_ptr<Device>> g_devs;
+
+// the device's phase clock when timing is on, else none
+const stl::PhaseClock* phase_clock(Device& d) { return g_phase_timing.load() ? &d.clock : nullptr; }
 
 bool fault_now() {
   long long v = g_fault_after.load(std::memory_order_relaxed);

@@ -1,5 +1,6 @@
 // stl_host.h -- what the host files of libstl share (stl_api.cpp and
-// stl_api_keyset.cpp, stl_api_authority.cpp, stl_api_sigcache.cpp): the fault
+// stl_api_keyset.cpp, stl_api_authority.cpp, stl_api_sigcache.cpp,
+// stl_api_shamap.cpp): the fault
 // countdown and the checked-call macros, the device, stream-context and buffer
 // types, the registry of live handle objects, the synchronous host call and
 // the by-key calls' miss path.  Host only: no .hip file includes it.  Every
@@ -220,10 +221,13 @@ struct StreamCtx {
   DevBuf scratch;
   // the by-key keyset calls' buffers (empty while a call has them out)
   ByKeyBufs bykey;
+  // stl_shamap_root_device's workspace (stl::shamap_workspace_bytes)
+  DevBuf shamap;
   void release() {
     if (auto_flag) (void)hipHostFree(auto_flag);
     auto_flag = auto_flag_dev = nullptr;
     bykey.release();
+    shamap.release();
     scratch.release();
     ws.release();
     queue.release();
@@ -247,7 +251,7 @@ struct StreamCtx {
   }
   bool holds_memory() const {
     return auto_flag || scratch.p || ws.p || queue.p || fork || keys || parsed[0] || parsed[1] || rdec.p || rready ||
-           done || bykey.holds();
+           done || bykey.holds() || shamap.p;
   }
   // moves every buffer and event of `o` into this (empty) context
   void adopt(StreamCtx& o) {
@@ -255,6 +259,7 @@ struct StreamCtx {
     std::swap(queue, o.queue);
     std::swap(scratch, o.scratch);
     std::swap(bykey, o.bykey);
+    std::swap(shamap, o.shamap);
     std::swap(fork, o.fork);
     std::swap(keys, o.keys);
     std::swap(parsed[0], o.parsed[0]);
@@ -353,6 +358,7 @@ int ctx_queue(StreamCtx& c, size_t n, uint32_t** qws, bool blob = false);
 uint32_t hash_grid(const Device& d);
 uint32_t hash_long_min(const Device& d, size_t n);
 unsigned long long* dev_counters(Device& d);
+const stl::PhaseClock* phase_clock(Device& d);  // the device's phase clock when timing is on, else none
 int check_flags(uint32_t flags);
 // the accept predicate's bits alone: what a keyset call or a cache may be given
 inline int check_keyset_flags(uint32_t flags) {

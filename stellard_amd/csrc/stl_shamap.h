@@ -1,0 +1,37 @@
+// stl_shamap.h -- launch interface between stl_api_shamap.cpp (host) and
+// stl_shamap.hip (gfx950 device code): the SHAMap root of a set of keys
+// (stl_shamap_root*).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "stl_kernels.h"
+
+namespace stl {
+
+// Workspace bytes per row besides the sort's own temporary storage: two 8-byte
+// sort words, two 4-byte row numbers (the sort's double buffers; the scan's
+// flags and the compacted rows reuse them), the neighbour byte, the sorted
+// keys and the hash slots (32 bytes each).
+constexpr size_t kShamapRowBytes = 8 + 8 + 4 + 4 + 1 + 32 + 32;
+constexpr size_t kShamapHeaderBytes = 512;  // 64 nodes-per-depth words, distinct and selected counts
+
+// What the radix sort and the scan of n rows want as temporary storage (the
+// larger of their needs; no device work), and the whole workspace of a call.
+hipError_t shamap_temp_bytes(size_t n, size_t* bytes);
+size_t shamap_workspace_bytes(size_t n, size_t temp_bytes);
+
+// Enqueues the whole computation on `stream`; no host wait.  key / leaf (or
+// null: the leaf hash is the key) n * 32 bytes, 16-byte aligned; select (or
+// null: every row) ceil(n / 64) words; ws of shamap_workspace_bytes, 256-byte
+// aligned.  root (32 bytes) and counts (4 words, or null) are written by the
+// last launch alone.  fault (or null): asked before every HIP call; true makes
+// the call fail there (stl_debug_fault_after).  clock (or null): marked before
+// the first launch (0) and after the sort (1), the heads and neighbours (2),
+// the levels (3) and the finish (4).  n >= 1.
+hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uint64_t* select, uint32_t n,
+                              uint8_t* root, uint32_t* counts, void* ws, size_t temp_bytes, bool (*fault)(),
+                              const PhaseClock* clock, hipStream_t stream);
+
+}  // namespace stl

@@ -755,6 +755,88 @@ class SigCache(_DeviceObject):
                 int(verified.value))
 
 
+# ---- SHAMap root (stl_shamap_root*) ----
+
+SHAMAP_MAX_ITEMS = N.STL_SHAMAP_MAX_ITEMS
+
+
+def _check_hashes(n, **ts):
+    """Keys, leaf hashes and the root are raw bytes: uint8, (n, 32)."""
+    import torch
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name} must be torch.uint8")
+        if tuple(t.shape) != (n, 32):
+            raise ValueError(f"{name} must be ({1 if name == 'out_root' else 'n'}, 32) bytes")
+
+
+def shamap_root_device(keys, leaf_hashes=None, select_words=None, out_root=None, counts=False, stream=None):
+    """stl_shamap_root_device: the SHAMap root of the set of keys (n, 32) uint8
+    in HBM -> (1, 32) uint8 root, or (root, int32[4] counts) with ``counts``
+    (True, or a tensor to write them to: distinct items, duplicates dropped,
+    inner nodes, deepest depth).  leaf_hashes (n, 32) or None (the leaf hash is
+    the key: a transaction set); select_words int64[ceil(n/64)] or None (every
+    row), the accept bitmaps' layout.  Asynchronous on ``stream``, no host
+    wait.  A deferred row's ID from a blob call is zero: clear its select bit
+    or supply its ID."""
+    import torch
+    if keys.dim() != 2:
+        raise ValueError("keys must be (n, 32) bytes")
+    n = keys.shape[0]
+    _check_hashes(n, keys=keys, leaf_hashes=leaf_hashes)
+    if n > SHAMAP_MAX_ITEMS:
+        raise ValueError("more than SHAMAP_MAX_ITEMS rows")
+    if select_words is not None and (select_words.dtype != torch.int64 or select_words.numel() < (n + 63) // 64):
+        raise ValueError("select_words must be int64, one word per 64 rows")
+    if out_root is None:
+        out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
+    _check_hashes(1, out_root=out_root)
+    cnt = None
+    if counts is True:
+        cnt = torch.empty(4, dtype=torch.int32, device=keys.device)
+    elif counts is not False and counts is not None:
+        cnt = counts
+        if cnt.dtype != torch.int32 or tuple(cnt.shape) != (4,):
+            raise ValueError("counts must be int32[4]")
+    for t in (keys, leaf_hashes, select_words, out_root, cnt):
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("device entry point needs contiguous CUDA tensors")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    N.check(N.load().stl_shamap_root_device(p(keys), p(leaf_hashes), p(select_words), n, p(out_root), p(cnt),
+                                            _stream_ptr(stream)), "stl_shamap_root_device")
+    return out_root if cnt is None else (out_root, cnt)
+
+
+def shamap_root(keys, leaf_hashes=None, select=None, counts=False):
+    """stl_shamap_root: host memory, synchronous.  keys (n, 32) uint8;
+    leaf_hashes (n, 32) or None; select: bool[n] or None -> 32 root bytes, or
+    (root, [4 counts]) with ``counts``."""
+    keys = np.ascontiguousarray(keys)
+    if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+        raise ValueError("keys must be (n, 32) uint8")
+    n = keys.shape[0]
+    if leaf_hashes is not None:
+        leaf_hashes = np.ascontiguousarray(leaf_hashes)
+        if leaf_hashes.dtype != np.uint8 or leaf_hashes.shape != (n, 32):
+            raise ValueError("leaf_hashes must be (n, 32) uint8")
+    sel = None
+    if select is not None:
+        select = np.asarray(select)
+        if select.dtype != np.bool_ or select.shape != (n,):
+            raise ValueError("select must be bool[n]")
+        sel = np.packbits(select, bitorder="little") if n else np.zeros(1, np.uint8)
+    if n > SHAMAP_MAX_ITEMS:
+        raise ValueError("more than SHAMAP_MAX_ITEMS rows")
+    root = np.zeros(32, dtype=np.uint8)
+    cnt = np.zeros(4, dtype=np.uint32)
+    N.check(N.load().stl_shamap_root(_buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n
+                                     else None, _buf(sel) if sel is not None else None, n, _buf(root), _buf(cnt)),
+            "stl_shamap_root")
+    return (root.tobytes(), [int(x) for x in cnt]) if counts else root.tobytes()
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
