@@ -904,6 +904,87 @@ int stl_shamap_root_device(const uint8_t *d_key, const uint8_t *d_leaf_hash, con
 int stl_shamap_root(const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *select_bitmap, size_t n,
                     uint8_t root[32], uint32_t counts[4]);
 
+/* ---- resident SHAMap: a state tree's root from each ledger's changes ----
+ * The state tree lives from ledger to ledger and holds millions of entries, of which a ledger
+ * changes a few thousand (Ledger::writeBack -> addGiveItem / updateGiveItem, Ledger.cpp:1228-1237;
+ * delItem, SHAMap.cpp:685); the node keeps the map in memory and rehashes only the paths it has
+ * touched (Ledger::updateHash, Ledger.cpp:273).  A stl_shamap_tree is the device-resident
+ * counterpart: the tree's distinct keys and leaf hashes, sorted, in device memory from one call to
+ * the next.  stl_shamap_tree_apply_device merges a batch of changes and leaves the new root in device
+ * memory; only the buckets the batch touches -- a bucket is the keys that share their first 4
+ * nibbles, 65,536 in all -- and the 4,369 nodes above the buckets are rehashed.
+ * CONTRACT: after every successful call the root is what stl_shamap_root_device gives for the
+ * tree's content, and the content is what the batches so far, read row by row, make of an empty map.
+ *
+ * A batch: d_key n * 32 bytes; d_leaf_hash n * 32 bytes, or NULL (the leaf hash is the key), not
+ * read for a delete; d_op n bytes, 0: set (insert or replace), nonzero: delete, or NULL (every row
+ * is a set).  The batch reads as a sequence of changes, like stl_acctdir_upsert: of rows with equal
+ * keys the last one counts.  d_root: 32 bytes; d_counts: 8 x uint32 or NULL: [0] items after the
+ * call, [1] inserted, [2] replaced, [3] deleted, [4] deletes of absent keys, [5] rows superseded by
+ * a later row with the same key, [6] dirty buckets (those that hold a change's key), [7] leaves
+ * gathered for rehashing (the items of the dirty buckets afterwards).  An apply to an empty tree is
+ * how a tree is loaded.
+ * Before any device work: a NULL tree, d_root, or d_key with n > 0, d_key or d_leaf_hash not 16-byte
+ * aligned, d_root or d_counts not 4-byte aligned, n > capacity, a handle that is not live or a tree
+ * of another device than the calling thread's is STL_EINVAL.  n == 0 is STL_OK and writes the
+ * current root (counts: the items and seven zeros).
+ * FAILURE: a call that returns a negative code leaves content, count and root as they were -- an
+ * apply writes only the generation that is not live, and the host turns to it after the call's last
+ * enqueue has succeeded; applying the same batch again then gives the right result.  The caller's
+ * outputs are written by the call's last kernel alone.
+ * CAPACITY AND SYNCHRONISATION: the ops are in device memory, so the host keeps an upper bound of
+ * the count: the last count it has read plus the rows of every apply since.  While bound + n <=
+ * capacity the call enqueues its fixed sequence on `stream` and returns without a host wait.
+ * Otherwise it waits on `stream` once, behind the batch's sort and locate steps (which write work
+ * areas alone), reads the exact count and the keys the batch inserts and deletes (20 bytes) and
+ * resets the bound; if the count after the batch would exceed the capacity it is STL_ENOMEM and the
+ * tree is unchanged -- so a full tree still takes replaces and deletes.  No kernel writes past the
+ * capacity whatever the data.
+ * COST: the merge moves every item into the other generation, O(items) bytes per apply (128 MiB at
+ * 2^20 items, read and written); the hashing is proportional to the dirty buckets.
+ * MEMORY: 193 B per row of capacity -- two generations of key and leaf hash (128 B), the scratch the
+ * dirty buckets' subtrees are hashed in (65 B: one bucket may hold everything) -- plus 5.9 MB of
+ * bucket values and per-bucket words, and per row of the largest batch 80 B in the tree and 89 B in
+ * the stream context's SHAMap workspace with the sort's temporary storage (as stl_shamap_root_device
+ * states it; never below what 65,536 rows ask for).
+ * Concurrency: calls on one tree are serialised by the caller, and a call on another stream must be
+ * ordered after the previous one by the caller; trees are independent of each other.  A tree lives
+ * on the device current at creation; stl_shutdown frees every tree.  The previous generation stays
+ * intact until the next apply.
+ * With stl_set_phase_timing on, an apply's batch sort and locate, merge, subtree and top-and-finish
+ * times are added to stl_stats.phase_ns[0..3] as one chunk. */
+typedef struct stl_shamap_tree stl_shamap_tree;
+typedef struct stl_shamap_tree_info {
+  uint32_t struct_size; /* sizeof(stl_shamap_tree_info) */
+  uint32_t capacity;
+  uint32_t items;
+  uint32_t bucket_depth; /* 4 */
+  int32_t device;        /* HIP device ordinal */
+  uint64_t bytes;        /* device memory the tree holds now */
+  uint8_t root[32];
+} stl_shamap_tree_info;
+/* capacity in 1..STL_SHAMAP_MAX_ITEMS.  Synchronous.  STL_OK and *out (an empty tree: root zero),
+ * or a negative code and *out = NULL. */
+int stl_shamap_tree_create(uint32_t capacity, stl_shamap_tree **out);
+/* Waits for the device, then frees the tree.  NULL, a destroyed handle and a handle from before
+ * stl_shutdown are ignored.  No call on the tree may be running on another thread. */
+void stl_shamap_tree_destroy(stl_shamap_tree *t);
+/* Waits for the device; the exact item count and the root. */
+int stl_shamap_tree_get_info(stl_shamap_tree *t, stl_shamap_tree_info *out);
+int stl_shamap_tree_apply_device(stl_shamap_tree *t, const uint8_t *d_key, const uint8_t *d_leaf_hash,
+                                 const uint8_t *d_op, size_t n, uint8_t *d_root, uint32_t *d_counts, void *stream);
+/* Host form: host memory (any alignment), synchronous: upload, the device form, 32 + 32 bytes back. */
+int stl_shamap_tree_apply(stl_shamap_tree *t, const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *op,
+                          size_t n, uint8_t root[32], uint32_t counts[8]);
+/* d_root (32 bytes, 4-byte aligned) <- the current root; asynchronous on `stream`. */
+int stl_shamap_tree_root_device(stl_shamap_tree *t, uint8_t *d_root, void *stream);
+/* The sorted content: d_key and d_leaf_hash (rows * 32 bytes each, 16-byte aligned, either may be
+ * NULL) <- the keys in memcmp order and their leaf hashes, *d_items (nullable) <- the item count;
+ * asynchronous on `stream`.  rows must be at least the host's bound of the count (see CAPACITY; the
+ * capacity always serves, and after stl_shamap_tree_get_info the bound is the count), else STL_EINVAL. */
+int stl_shamap_tree_export_device(stl_shamap_tree *t, uint8_t *d_key, uint8_t *d_leaf_hash, size_t rows,
+                                  uint32_t *d_items, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,13 @@ SYMBOLS = [
      [_P, _U8P, _P, _P, ctypes.c_size_t, _U8P, _U8P, _U8P, ctypes.c_uint32, _P, _P]),
     ("stl_shamap_root_device", ctypes.c_int, [_U8P, _U8P, _P, ctypes.c_size_t, _U8P, _P, _P]),
     ("stl_shamap_root", ctypes.c_int, [_U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P]),
+    ("stl_shamap_tree_create", ctypes.c_int, [ctypes.c_uint32, _P]),
+    ("stl_shamap_tree_destroy", None, [_P]),
+    ("stl_shamap_tree_get_info", ctypes.c_int, [_P, _P]),
+    ("stl_shamap_tree_apply_device", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_tree_apply", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P]),
+    ("stl_shamap_tree_root_device", ctypes.c_int, [_P, _U8P, _P]),
+    ("stl_shamap_tree_export_device", ctypes.c_int, [_P, _U8P, _U8P, ctypes.c_size_t, _P, _P]),
 ]
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

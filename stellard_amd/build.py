@@ -15,6 +15,8 @@
                                  and insert
   tests/native/libhostemu_shamap.so  the SHAMap root's nibble, common prefix,
                                  node rule and inner-node hash
+  tests/native/libhostemu_shamap_tree.so  the resident SHAMap's bucket, delta,
+                                 position and top rules and its staged apply
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -32,9 +34,9 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
-                "stl_shamap.hip", "stl_selftest.hip",
+                "stl_shamap.hip", "stl_shamap_tree.hip", "stl_selftest.hip",
                 "stl_api.cpp", "stl_api_keyset.cpp", "stl_api_authority.cpp", "stl_api_sigcache.cpp",
-                "stl_api_shamap.cpp", "stl_batcher.cpp"]
+                "stl_api_shamap.cpp", "stl_api_shamap_tree.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
                                "stl_sc25519.h", "stl_sha512.h", "stl_base_table.h", "stl_lattice.h", "stl_txblob.h", "stl_sign.h",
                                "stl_comb.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h",
@@ -42,6 +44,7 @@ PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe2551
                                "stl_acctdir_core.h", "stl_acctdir.h",
                                "stl_sigcache_core.h", "stl_sigcache.h",
                                "stl_shamap_core.h", "stl_shamap.h",
+                               "stl_shamap_tree_core.h", "stl_shamap_tree.h",
                                "stl_group.h", "stl_selftest.h", "stl_host.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
@@ -76,7 +79,8 @@ def _run(cmd, cwd=ROOT):
 # (about 100 s) -- the objects live in build/obj (git-ignored, never shipped)
 HOST_ONLY = ["stl_host.h"]
 HOST_DEPS = HOST_ONLY + ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
-             "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", "stl_shamap.h", os.path.join("..", "..", "include", "stl.h")]
+             "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", "stl_shamap.h",
+             "stl_shamap_tree.h", "stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -141,6 +145,8 @@ SMALL_HARNESSES = {
                                         "stl_sha512.h", "stl_fe25519.h")),
     "sigcache": ("hostemu_sigcache.cpp", ("stl_sigcache_core.h",)),
     "shamap": ("hostemu_shamap.cpp", ("stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
+    "shamap_tree": ("hostemu_shamap_tree.cpp", ("stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
+                                                "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -190,6 +196,10 @@ def build_hostemu_shamap(force=False):
     return _build_small("shamap", force)
 
 
+def build_hostemu_shamap_tree(force=False):
+    return _build_small("shamap_tree", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -213,7 +223,7 @@ def main(argv=None):
                 ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force),
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
-                ex.submit(build_hostemu_shamap, force)]
+                ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force)]
         for j in jobs:
             j.result()
     build_oracle()

@@ -1,0 +1,246 @@
+// stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
+// ledger's changes): the stl_shamap_tree_* entry points of include/stl.h;
+// kernels: stl_shamap_tree.hip, and the sort and level kernels of stl_shamap.hip.
+#include "stl_host.h"
+#include "stl_shamap.h"
+#include "stl_shamap_tree.h"
+#include "stl_shamap_tree_core.h"
+
+using namespace stl;
+
+// One tree: on one device two generations of (sorted keys, leaf hashes, bucket
+// values, count, root) and the work areas of an apply.  `live` names the
+// generation that holds the tree; an apply writes the other and the host flips
+// `live` once the apply's last enqueue has succeeded, so a failed call leaves
+// the tree as it was.  `bound`: the last count the host has read plus the rows
+// of every apply since -- never below the count on the device.
+struct stl_shamap_tree {
+  int ordinal = -1;
+  uint32_t capacity = 0;
+  int live = 0;
+  uint32_t bound = 0;
+  DevBuf rows[2];  // keys, then leaf hashes: 64 B per row of capacity
+  DevBuf genfix;   // both generations' bucket values and meta words
+  DevBuf fixed, batch, scratch;
+  stl::TreeGen gen(int g) const {
+    stl::TreeGen o;
+    o.key = static_cast<uint8_t*>(rows[g].p);
+    o.leaf = o.key + 32 * (size_t)capacity;
+    uint8_t* p = static_cast<uint8_t*>(genfix.p) + (size_t)g * stl::shamap_tree_gen_fixed_bytes();
+    o.bcnt = reinterpret_cast<uint32_t*>(p);
+    o.bh = reinterpret_cast<uint32_t*>(p + align256(4 * stl::kTreeBuckets));
+    o.meta = reinterpret_cast<uint32_t*>(p + align256(4 * stl::kTreeBuckets) + align256(32 * stl::kTreeBuckets));
+    return o;
+  }
+  uint64_t bytes() const {
+    return (uint64_t)rows[0].cap + rows[1].cap + genfix.cap + fixed.cap + batch.cap + scratch.cap;
+  }
+  void release() {
+    rows[0].release();
+    rows[1].release();
+    genfix.release();
+    fixed.release();
+    batch.release();
+    scratch.release();
+  }
+};
+
+namespace {
+// Handle first: a handle that is not live is STL_EINVAL on every machine.
+LiveSet<stl_shamap_tree, CheckFirst::kHandle> g_trees;
+
+int check_apply_args(const stl_shamap_tree* t, const void* key, const void* leaf, size_t n, const void* root,
+                     const void* counts, bool device_form) {
+  if (!t || !root || n > STL_SHAMAP_MAX_ITEMS || (n && !key)) return STL_EINVAL;
+  if (!device_form) return STL_OK;  // host arrays: any alignment serves
+  if (((uintptr_t)key & 15u) != 0 || ((uintptr_t)leaf & 15u) != 0) return STL_EINVAL;
+  if (((uintptr_t)root & 3u) != 0 || ((uintptr_t)counts & 3u) != 0) return STL_EINVAL;
+  return STL_OK;
+}
+
+// One apply of n >= 1 rows on stream s (g_trees.mu held, t live on d):
+// enqueued, and waited for only when the host's bound of the count no longer
+// admits the batch.  Nothing of *t changes here; the caller commits.
+int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf, const uint8_t* d_op,
+                 size_t n, uint8_t* d_root, uint32_t* d_counts, hipStream_t s, uint32_t* bound) {
+  const bool fits = (uint64_t)t->bound + n <= t->capacity;
+  size_t temp = 0, temp_buckets = 0;
+  STL_TRY(stl::shamap_temp_bytes(n, &temp));
+  STL_TRY(stl::shamap_temp_bytes(stl::kTreeBuckets, &temp_buckets));
+  if (temp_buckets > temp) temp = temp_buckets;
+  const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
+  std::lock_guard<std::mutex> lk(c->mu);
+  STL_RC(c->shamap.ensure(stl::shamap_workspace_bytes(n, temp)));
+  STL_RC(t->batch.ensure(stl::shamap_tree_batch_bytes(n)));
+  stl::TreeApply a;
+  a.from = t->gen(t->live);
+  a.to = t->gen(t->live ^ 1);
+  a.capacity = t->capacity;
+  a.items_bound = t->bound;
+  a.after_bound = fits ? t->bound + (uint32_t)n : t->capacity;
+  a.fixed = t->fixed.p;
+  a.batch = t->batch.p;
+  a.scratch = t->scratch.p;
+  a.sort_ws = c->shamap.p;
+  a.temp_bytes = temp;
+  STL_TRY(stl::launch_shamap_tree_locate(a, d_key, d_leaf, d_op, (uint32_t)n, fault_now, phase_clock(d), s));
+  if (!fits) {
+    // the bound no longer admits the batch: the one wait, for the exact count
+    // and what the batch inserts and deletes.  Only the work areas have been
+    // written so far, so a refusal leaves the tree as it was.
+    uint32_t count = 0, cc[4] = {};
+    STL_TRY(hipMemcpyAsync(&count, a.from.meta, 4, hipMemcpyDeviceToHost, s));
+    STL_TRY(hipMemcpyAsync(cc, stl::shamap_tree_change_counts(t->fixed.p), sizeof(cc), hipMemcpyDeviceToHost, s));
+    STL_TRY(hipStreamSynchronize(s));
+    if (count > t->bound || cc[3] > count || cc[1] > n) return STL_EHIP;
+    t->bound = count;
+    const uint64_t after = (uint64_t)count - cc[3] + cc[1];
+    if (after > t->capacity) return STL_ENOMEM;
+    a.items_bound = count;
+    a.after_bound = after ? (uint32_t)after : 1u;
+    *bound = (uint32_t)after;
+  } else {
+    *bound = t->bound + (uint32_t)n;
+  }
+  STL_TRY(stl::launch_shamap_tree_merge(a, (uint32_t)n, d_root, d_counts, fault_now, phase_clock(d), s));
+  return STL_OK;
+}
+
+void tree_commit(stl_shamap_tree* t, uint32_t bound_after) {
+  t->live ^= 1;
+  t->bound = bound_after;
+}
+}  // namespace
+
+extern "C" {
+
+int stl_shamap_tree_create(uint32_t capacity, stl_shamap_tree** out) {
+  if (out) *out = nullptr;
+  if (!out || capacity == 0 || capacity > STL_SHAMAP_MAX_ITEMS) return STL_EINVAL;
+  Device* d = nullptr;
+  STL_RC(device_for_call(&d));
+  std::unique_ptr<stl_shamap_tree> t(new stl_shamap_tree());
+  t->ordinal = d->ordinal;
+  t->capacity = capacity;
+  DeviceGuard guard;
+  auto go = [&]() -> int {
+    std::lock_guard<std::mutex> lk(d->mu);
+    STL_TRY(hipSetDevice(d->ordinal));
+    STL_RC(t->rows[0].ensure(64 * (size_t)capacity));
+    STL_RC(t->rows[1].ensure(64 * (size_t)capacity));
+    STL_RC(t->genfix.ensure(2 * stl::shamap_tree_gen_fixed_bytes()));
+    STL_RC(t->fixed.ensure(stl::shamap_tree_fixed_bytes()));
+    STL_RC(t->scratch.ensure(stl::shamap_tree_scratch_bytes(capacity)));
+    // the empty tree: no key in any bucket, count zero, root zero -- in both generations
+    STL_TRY(hipMemsetAsync(t->genfix.p, 0, 2 * stl::shamap_tree_gen_fixed_bytes(), d->stream));
+    STL_TRY(hipStreamSynchronize(d->stream));
+    return STL_OK;
+  };
+  const int rc = go();
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    t->release();
+    return rc;
+  }
+  g_trees.add(*out = t.release());
+  return STL_OK;
+}
+
+void stl_shamap_tree_destroy(stl_shamap_tree* t) { g_trees.destroy(t); }
+
+int stl_shamap_tree_get_info(stl_shamap_tree* t, stl_shamap_tree_info* out) {
+  if (!out || out->struct_size != sizeof(stl_shamap_tree_info)) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  if (!g_trees.live(t)) return STL_EINVAL;
+  uint32_t meta[stl::kTreeMetaWords] = {};
+  {
+    DeviceGuard guard;
+    STL_TRY(hipSetDevice(t->ordinal));
+    STL_TRY(hipDeviceSynchronize());
+    STL_TRY(hipMemcpy(meta, t->gen(t->live).meta, sizeof(meta), hipMemcpyDeviceToHost));
+  }
+  t->bound = meta[0];
+  out->capacity = t->capacity;
+  out->items = meta[0];
+  out->bucket_depth = stl::kTreeBucketDepth;
+  out->device = t->ordinal;
+  out->bytes = t->bytes();
+  std::memcpy(out->root, meta + stl::kTreeMetaRoot, 32);
+  return STL_OK;
+}
+
+int stl_shamap_tree_apply_device(stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf_hash,
+                                 const uint8_t* d_op, size_t n, uint8_t* d_root, uint32_t* d_counts, void* stream) {
+  STL_RC(check_apply_args(t, d_key, d_leaf_hash, n, d_root, d_counts, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  if (n > t->capacity) return STL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, s));
+    return STL_OK;
+  }
+  uint32_t bound = 0;
+  STL_RC(tree_enqueue(*d, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, s, &bound));
+  tree_commit(t, bound);
+  return STL_OK;
+}
+
+int stl_shamap_tree_apply(stl_shamap_tree* t, const uint8_t* key, const uint8_t* leaf_hash, const uint8_t* op,
+                          size_t n, uint8_t root[32], uint32_t counts[8]) {
+  STL_RC(check_apply_args(t, key, leaf_hash, n, root, counts, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(g_trees.for_call(t, &dp));
+  if (n > t->capacity) return STL_EINVAL;
+  uint32_t bound = 0;
+  HostCall call("stl_shamap_tree_apply", n, *dp);
+  const int rc = call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(d.txid.ensure(32));
+    STL_RC(d.status.ensure(32));
+    uint8_t* d_root = static_cast<uint8_t*>(d.txid.p);
+    uint32_t* d_counts = static_cast<uint32_t*>(d.status.p);
+    if (n == 0) {
+      STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, d.stream));
+    } else {
+      STL_RC(call.upload(d.pk, key, n * 32));
+      if (leaf_hash) STL_RC(call.upload(d.msg, leaf_hash, n * 32));
+      if (op) STL_RC(call.upload(d.sig, op, n));
+      STL_RC(tree_enqueue(d, t, static_cast<const uint8_t*>(d.pk.p),
+                          leaf_hash ? static_cast<const uint8_t*>(d.msg.p) : nullptr,
+                          op ? static_cast<const uint8_t*>(d.sig.p) : nullptr, n, d_root, d_counts, d.stream, &bound));
+    }
+    call.download(root, d.txid, 32);
+    call.download(counts, d.status, 32);
+    return STL_OK;
+  });
+  if (rc == STL_OK && n) tree_commit(t, bound);  // only once the results are back
+  return rc;
+}
+
+int stl_shamap_tree_root_device(stl_shamap_tree* t, uint8_t* d_root, void* stream) {
+  if (!t || !d_root || ((uintptr_t)d_root & 3u) != 0) return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, nullptr, static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+int stl_shamap_tree_export_device(stl_shamap_tree* t, uint8_t* d_key, uint8_t* d_leaf_hash, size_t rows,
+                                  uint32_t* d_items, void* stream) {
+  if (!t || rows > STL_SHAMAP_MAX_ITEMS) return STL_EINVAL;
+  if (((uintptr_t)d_key & 15u) != 0 || ((uintptr_t)d_leaf_hash & 15u) != 0 || ((uintptr_t)d_items & 3u) != 0)
+    return STL_EINVAL;
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  if (rows < t->bound) return STL_EINVAL;
+  STL_TRY(stl::launch_shamap_tree_export(t->gen(t->live), t->bound, d_key, d_leaf_hash, (uint32_t)rows, d_items,
+                                         static_cast<hipStream_t>(stream)));
+  return STL_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@ namespace stl {
 // keys and the hash slots (32 bytes each).
 constexpr size_t kShamapRowBytes = 8 + 8 + 4 + 4 + 1 + 32 + 32;
 constexpr size_t kShamapHeaderBytes = 512;  // 64 nodes-per-depth words, distinct and selected counts
+constexpr uint32_t kShamapHdrDistinct = 64;  // the header word that holds the number of sorted distinct keys
 
 // What the radix sort and the scan of n rows want as temporary storage (the
 // larger of their needs; no device work), and the whole workspace of a call.
@@ -33,5 +34,34 @@ size_t shamap_workspace_bytes(size_t n, size_t temp_bytes);
 hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uint64_t* select, uint32_t n,
                               uint8_t* root, uint32_t* counts, void* ws, size_t temp_bytes, bool (*fault)(),
                               const PhaseClock* clock, hipStream_t stream);
+
+// ---- the parts the resident tree (stl_shamap_tree.hip) runs on arrays of its own ----
+// The same sort passes over n keys in a workspace of shamap_workspace_bytes(n,
+// temp_bytes): perm[i] is the row at sorted position i (stable: equal keys in
+// row order).  flags / idx: two arrays of n words of the workspace that are
+// free once the sort is done (the root's head flags and their scan live
+// there); temp: the workspace's temporary storage of temp_bytes.
+struct ShamapSorted {
+  const uint32_t* perm;
+  uint32_t* flags;
+  uint32_t* idx;
+  void* temp;
+};
+hipError_t launch_shamap_sort(const uint8_t* key, uint32_t n, void* ws, size_t temp_bytes, bool (*fault)(),
+                              hipStream_t stream, ShamapSorted* out);
+// The temporary storage within a workspace of shamap_workspace_bytes(n, temp_bytes).
+void* shamap_workspace_temp(size_t n, void* ws, size_t temp_bytes);
+// out[i] = in[0] + .. + in[i - 1] (mod 2^32) over n words; temp of at least
+// shamap_temp_bytes(n).
+hipError_t shamap_exclusive_scan(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, size_t n,
+                                 bool (*fault)(), hipStream_t stream);
+// The neighbour kernel and the level kernel for depths d_first down to d_last
+// over sorted distinct keys skey with their hash slots: hdr (kShamapHeaderBytes,
+// zero but for hdr[kShamapHdrDistinct] = the number of keys, read on the
+// device); n: a host-known bound of that number, which sizes the grids and the
+// neighbour bytes l.  Afterwards the slot of the first key of every node at
+// depth d_last holds that node's hash.
+hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
+                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream);
 
 }  // namespace stl

@@ -32,6 +32,10 @@
 // position, one 32-byte load.  Then every lane hashes one record out of LDS:
 // 129 dwords apart, an odd stride, so the lanes of a wave read 64 different
 // banks.  128 records are 66,048 bytes: two workgroups fit a CU's 160 KB.
+//
+// The resident tree (stl_shamap_tree.hip) runs the sort passes, the scan and
+// the neighbour and level kernels for a range of depths on arrays of its own
+// (launch_shamap_sort, shamap_exclusive_scan, launch_shamap_levels).
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -51,7 +55,7 @@ constexpr uint32_t kSmLevelGrid = 1024;  // the level kernel's fixed grid: spans
 constexpr uint32_t kSmSpansWanted = 512; // workgroups a depth is spread over before they are filled further
 constexpr uint32_t kSmSpanChunksMax = 16;  // chunks of 256 positions one workgroup walks at most per span
 // header words (kShamapHeaderBytes)
-constexpr uint32_t kHdrDistinct = 64, kHdrSelected = 65;
+constexpr uint32_t kHdrDistinct = kShamapHdrDistinct, kHdrSelected = 65;
 
 __device__ __forceinline__ void sm_st8(uint8_t* p, size_t row, const uint32_t k[8]) {
   uint4* q = reinterpret_cast<uint4*>(p + 32 * row);
@@ -347,6 +351,20 @@ size_t shamap_workspace_bytes(size_t n, size_t temp_bytes) { return ShamapWs(nul
     if (e_ != hipSuccess) return e_;                                    \
   } while (0)
 
+// The four stable radix passes over (sort word, row), least significant word first.
+static hipError_t shamap_sort_passes(const uint8_t* key, uint32_t n, const ShamapWs& w, size_t temp_bytes,
+                                     rocprim::double_buffer<uint64_t>& k64, rocprim::double_buffer<uint32_t>& v,
+                                     bool (*fault)(), hipStream_t stream) {
+  const uint32_t g = grid_of(n);
+  for (int word = 3; word >= 0; --word) {
+    SM_LAUNCH(shamap_sort_word_kernel, g, kSmBlock, key, word == 3 ? nullptr : v.current(), n, (uint32_t)word,
+              k64.current(), v.current());
+    size_t tb = temp_bytes;
+    SM_TRY(rocprim::radix_sort_pairs(w.temp, tb, k64, v, n, 0, 64, stream));
+  }
+  return hipSuccess;
+}
+
 hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uint64_t* select, uint32_t n,
                               uint8_t* root, uint32_t* counts, void* ws, size_t temp_bytes, bool (*fault)(),
                               const PhaseClock* clock, hipStream_t stream) {
@@ -360,11 +378,9 @@ hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uin
   // 1. sort
   rocprim::double_buffer<uint64_t> k64(w.k[0], w.k[1]);
   rocprim::double_buffer<uint32_t> v(w.v[0], w.v[1]);
-  for (int word = 3; word >= 0; --word) {
-    SM_LAUNCH(shamap_sort_word_kernel, g, kSmBlock, key, word == 3 ? nullptr : v.current(), n, (uint32_t)word,
-              k64.current(), v.current());
-    size_t tb = temp_bytes;
-    SM_TRY(rocprim::radix_sort_pairs(w.temp, tb, k64, v, n, 0, 64, stream));
+  {
+    const hipError_t e = shamap_sort_passes(key, n, w, temp_bytes, k64, v, fault, stream);
+    if (e != hipSuccess) return e;
   }
   if (select) {
     rocprim::double_buffer<uint32_t> k32(reinterpret_cast<uint32_t*>(w.k[0]), reinterpret_cast<uint32_t*>(w.k[1]));
@@ -392,6 +408,42 @@ hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uin
   // 5. finish
   SM_LAUNCH(shamap_finish_kernel, 1, 64, w.hdr, w.slot, reinterpret_cast<uint32_t*>(root), counts);
   if (clock) clock->mark(clock->ctx, stream, 4);
+  return hipSuccess;
+}
+
+hipError_t launch_shamap_sort(const uint8_t* key, uint32_t n, void* ws, size_t temp_bytes, bool (*fault)(),
+                              hipStream_t stream, ShamapSorted* out) {
+  if (n == 0 || !key || !ws || !out || ((uintptr_t)key & 15u) || ((uintptr_t)ws & 255u)) return hipErrorInvalidValue;
+  const ShamapWs w(ws, n, temp_bytes);
+  rocprim::double_buffer<uint64_t> k64(w.k[0], w.k[1]);
+  rocprim::double_buffer<uint32_t> v(w.v[0], w.v[1]);
+  const hipError_t e = shamap_sort_passes(key, n, w, temp_bytes, k64, v, fault, stream);
+  if (e != hipSuccess) return e;
+  out->perm = v.current();
+  out->flags = reinterpret_cast<uint32_t*>(w.k[0]);
+  out->idx = reinterpret_cast<uint32_t*>(w.k[1]);
+  out->temp = w.temp;
+  return hipSuccess;
+}
+
+void* shamap_workspace_temp(size_t n, void* ws, size_t temp_bytes) { return ShamapWs(ws, n, temp_bytes).temp; }
+
+hipError_t shamap_exclusive_scan(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, size_t n,
+                                 bool (*fault)(), hipStream_t stream) {
+  size_t tb = temp_bytes;
+  SM_TRY(rocprim::exclusive_scan(temp, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), stream));
+  return hipSuccess;
+}
+
+hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
+                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream) {
+  if (n == 0 || !hdr || !l || !skey || !slot || d_first >= kShamapDepths || d_last > d_first)
+    return hipErrorInvalidValue;
+  const uint32_t g = grid_of(n);
+  SM_LAUNCH(shamap_neighbour_kernel, g, kSmBlock, skey, n, l, hdr);
+  const uint32_t lg = g < kSmLevelGrid ? g : kSmLevelGrid;
+  for (int d = (int)d_first; d >= (int)d_last; --d)
+    SM_LAUNCH(shamap_level_kernel, lg, kSmBlock, hdr, l, skey, slot, (uint32_t)d);
   return hipSuccess;
 }
 

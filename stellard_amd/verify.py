@@ -837,6 +837,130 @@ def shamap_root(keys, leaf_hashes=None, select=None, counts=False):
     return (root.tobytes(), [int(x) for x in cnt]) if counts else root.tobytes()
 
 
+# ---- resident SHAMap (stl_shamap_tree_*) ----
+
+class ShamapTreeInfo(ctypes.Structure):
+    """stl_shamap_tree_info (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("capacity", ctypes.c_uint32), ("items", ctypes.c_uint32),
+                ("bucket_depth", ctypes.c_uint32), ("device", ctypes.c_int32), ("bytes", ctypes.c_uint64),
+                ("root", ctypes.c_uint8 * 32)]
+
+
+class ShamapTree(_DeviceObject):
+    """A device-resident SHAMap (stl_shamap_tree_create): the tree's keys and
+    leaf hashes stay in HBM, ``apply_device`` merges a batch of changes (set or
+    delete per row; of equal keys the last row counts) and gives the new root,
+    rehashing only the buckets the batch touches.
+
+        with ShamapTree(capacity) as t:
+            t.apply_device(keys, leaf_hashes)                 # load
+            root = t.apply_device(changed, new_hashes, ops)   # each ledger
+    """
+
+    _prefix, _Info = "stl_shamap_tree", ShamapTreeInfo
+
+    def __init__(self, capacity):
+        h = ctypes.c_void_p()
+        N.check(N.load().stl_shamap_tree_create(int(capacity), ctypes.byref(h)), "stl_shamap_tree_create")
+        self._h = h
+
+    def info(self):
+        """Waits for the device: capacity, exact items, bucket_depth, device,
+        bytes, root (32 bytes)."""
+        i = super().info()
+        i["root"] = bytes(i["root"])
+        return i
+
+    def apply_device(self, keys, leaf_hashes=None, ops=None, out_root=None, counts=False, stream=None):
+        """stl_shamap_tree_apply_device: keys (n, 32) uint8 in HBM, leaf_hashes
+        (n, 32) or None (the leaf hash is the key), ops uint8[n] (0 set, else
+        delete) or None (all sets) -> (1, 32) uint8 root, or (root, int32[8]
+        counts) with ``counts`` (True, or a tensor to write them to).
+        Asynchronous on ``stream``."""
+        import torch
+        if keys.dim() != 2:
+            raise ValueError("keys must be (n, 32) bytes")
+        n = keys.shape[0]
+        _check_hashes(n, keys=keys, leaf_hashes=leaf_hashes)
+        if ops is not None and (ops.dtype != torch.uint8 or tuple(ops.shape) != (n,)):
+            raise ValueError("ops must be uint8[n]")
+        if out_root is None:
+            out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
+        _check_hashes(1, out_root=out_root)
+        cnt = None
+        if counts is True:
+            cnt = torch.empty(8, dtype=torch.int32, device=keys.device)
+        elif counts is not False and counts is not None:
+            cnt = counts
+            if cnt.dtype != torch.int32 or tuple(cnt.shape) != (8,):
+                raise ValueError("counts must be int32[8]")
+        for t in (keys, leaf_hashes, ops, out_root, cnt):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_shamap_tree_apply_device(self._h, p(keys), p(leaf_hashes), p(ops), n, p(out_root), p(cnt),
+                                                      _stream_ptr(stream)), "stl_shamap_tree_apply_device")
+        return out_root if cnt is None else (out_root, cnt)
+
+    def apply(self, keys, leaf_hashes=None, ops=None, counts=False):
+        """stl_shamap_tree_apply: host memory, synchronous.  keys (n, 32) uint8,
+        leaf_hashes (n, 32) or None, ops uint8[n] or bool[n] or None -> 32 root
+        bytes, or (root, [8 counts]) with ``counts``."""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+            raise ValueError("keys must be (n, 32) uint8")
+        n = keys.shape[0]
+        if leaf_hashes is not None:
+            leaf_hashes = np.ascontiguousarray(leaf_hashes)
+            if leaf_hashes.dtype != np.uint8 or leaf_hashes.shape != (n, 32):
+                raise ValueError("leaf_hashes must be (n, 32) uint8")
+        if ops is not None:
+            ops = np.ascontiguousarray(ops)
+            if ops.dtype not in (np.uint8, np.bool_) or ops.shape != (n,):
+                raise ValueError("ops must be uint8[n] or bool[n]")
+            ops = ops.astype(np.uint8)
+        root = np.zeros(32, dtype=np.uint8)
+        cnt = np.zeros(8, dtype=np.uint32)
+        N.check(N.load().stl_shamap_tree_apply(
+            self._h, _buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n else None,
+            _buf(ops) if ops is not None and n else None, n, _buf(root), _buf(cnt)), "stl_shamap_tree_apply")
+        return (root.tobytes(), [int(x) for x in cnt]) if counts else root.tobytes()
+
+    def root_device(self, out_root=None, stream=None):
+        """The current root -> (1, 32) uint8 CUDA tensor (async on ``stream``)."""
+        import torch
+        if out_root is None:
+            out_root = torch.empty((1, 32), dtype=torch.uint8, device="cuda")
+        _check_hashes(1, out_root=out_root)
+        if not out_root.is_cuda or not out_root.is_contiguous():
+            raise ValueError("device entry point needs contiguous CUDA tensors")
+        N.check(N.load().stl_shamap_tree_root_device(self._h, ctypes.c_void_p(out_root.data_ptr()),
+                                                     _stream_ptr(stream)), "stl_shamap_tree_root_device")
+        return out_root
+
+    def export_device(self, out_keys, out_leaf_hashes=None, out_items=None, stream=None):
+        """The sorted content -> out_keys / out_leaf_hashes ((rows, 32) uint8
+        CUDA tensors, rows at least the host's bound of the count: the capacity
+        always serves) and out_items (int32[1], made when None).  Returns
+        out_items; async on ``stream``."""
+        import torch
+        if out_keys.dim() != 2:
+            raise ValueError("out_keys must be (n, 32) bytes")
+        rows = out_keys.shape[0]
+        _check_hashes(rows, out_keys=out_keys, out_leaf_hashes=out_leaf_hashes)
+        if out_items is None:
+            out_items = torch.zeros(1, dtype=torch.int32, device=out_keys.device)
+        if out_items.dtype != torch.int32 or out_items.numel() != 1:
+            raise ValueError("out_items must be int32[1]")
+        for t in (out_keys, out_leaf_hashes, out_items):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_shamap_tree_export_device(self._h, p(out_keys), p(out_leaf_hashes), rows, p(out_items),
+                                                       _stream_ptr(stream)), "stl_shamap_tree_export_device")
+        return out_items
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
