@@ -985,6 +985,64 @@ int stl_shamap_tree_root_device(stl_shamap_tree *t, uint8_t *d_root, void *strea
 int stl_shamap_tree_export_device(stl_shamap_tree *t, uint8_t *d_key, uint8_t *d_leaf_hash, size_t rows,
                                   uint32_t *d_items, void *stream);
 
+/* ---- SHAMap inner nodes: what flushDirty writes, per set and per apply ----
+ * Right after applyTransactions a node flushes both maps (LedgerConsensus.cpp:993-996 -> flushDirty,
+ * SHAMap.cpp:972): every inner node the ledger changed goes to the node store, keyed by its hash,
+ * its body "MIN\0" followed by the 16 child hashes (SHAMapTreeNode::addRaw, snfPREFIX); the same 512
+ * bytes are what a peer acquiring a set or a ledger asks for (getNodeFat, getFetchPack).  The two
+ * calls below are stl_shamap_root_device and stl_shamap_tree_apply_device -- the same root, counts,
+ * duplicate rule, capacity rule, failure contract and argument checks -- and also write the inner
+ * nodes they hash on the way.  Leaf nodes are the caller's: it holds the leaf blobs, and a node's
+ * leaf mask tells which of its child hashes are leaf hashes.
+ *
+ * stl_shamap_nodes_device writes every inner node of the map exactly once: *count == counts[2].
+ * stl_shamap_tree_apply_nodes_device writes the set E of the NEW tree's inner nodes, each once.  With
+ * the dirty buckets those that hold the key of any row of the batch (counts[6]), E is every inner
+ * node at depth >= 4 whose first four nibbles are a dirty bucket, and every inner node at depth < 4
+ * (the root whenever the new tree holds a key) whose prefix is a prefix of a dirty bucket.
+ * GUARANTEE: every inner node of the new tree whose hash is not the hash of an inner node of the old
+ * tree is in E -- such a node has a changed key beneath it.  E may also hold unchanged nodes of dirty
+ * buckets; a node store keyed by hash drops those.  With n == 0, *count = 0.
+ * ORDER: the order of the rows is unspecified and may differ from run to run.
+ * OVERFLOW: rows are written only at indices < max_nodes.  When *count > max_nodes the arrays hold
+ * some max_nodes of the nodes and root and counts are still right; the caller then calls again with
+ * room -- for a tree, stl_shamap_tree_export_device followed by stl_shamap_nodes_device.  A map of m
+ * keys has at most 63 (m - 1) + 1 inner nodes.  No kernel stores past max_nodes rows whatever the data.
+ * FAILURE: *count is written by the call's last kernel alone (for n == 0 of the set call, by a
+ * memset as root and counts are); the four arrays may be partly written by a call that fails.  A tree
+ * is unchanged by a failed call.
+ * Before any device work, besides the checks of the calls they extend: a NULL out, hash, body or
+ * count, a struct_size other than sizeof(stl_shamap_nodes_out), max_nodes > STL_SHAMAP_MAX_NODES,
+ * and in the device form hash, body or id not 16-byte aligned or meta or count not 4-byte aligned
+ * is STL_EINVAL.
+ * SYNCHRONISATION: the device forms wait where the calls they extend wait, nowhere else.  The host
+ * forms stage max_nodes * 580 bytes on the device, wait once for the count (4 bytes) and copy back
+ * min(*count, max_nodes) rows; a host array may have any alignment. */
+#define STL_SHAMAP_MAX_NODES 0xffffffc0u
+#define STL_SHAMAP_NODE_BODY_BYTES 512u
+typedef struct stl_shamap_nodes_out {
+  uint32_t struct_size; /* sizeof(stl_shamap_nodes_out) */
+  uint32_t max_nodes;   /* rows the four arrays have room for */
+  uint8_t *hash;        /* max_nodes * 32: the node's hash = its node-store key */
+  uint8_t *body;        /* max_nodes * 512: child hashes 0..15, zeros for an empty branch;
+                           "MIN\0" || body is the snfPREFIX blob, SHA512Half of it = hash */
+  uint8_t *id;          /* max_nodes * 32 or NULL: the key's first `depth` nibbles, rest 0
+                           (SHAMapNodeID's masked key) */
+  uint32_t *meta;       /* max_nodes or NULL: bits 0-7 depth (0..63), bits 8-15 zero,
+                           bit 16+c set = branch c is a leaf (non-empty and holding one key) */
+  uint32_t *count;      /* one word, required: nodes the call produced, may exceed max_nodes */
+} stl_shamap_nodes_out;
+int stl_shamap_nodes_device(const uint8_t *d_key, const uint8_t *d_leaf_hash, const uint64_t *d_select_words,
+                            size_t n, uint8_t *d_root, uint32_t *d_counts, const stl_shamap_nodes_out *out,
+                            void *stream);
+int stl_shamap_nodes(const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *select_bitmap, size_t n,
+                     uint8_t root[32], uint32_t counts[4], const stl_shamap_nodes_out *out);
+int stl_shamap_tree_apply_nodes_device(stl_shamap_tree *t, const uint8_t *d_key, const uint8_t *d_leaf_hash,
+                                       const uint8_t *d_op, size_t n, uint8_t *d_root, uint32_t *d_counts,
+                                       const stl_shamap_nodes_out *out, void *stream);
+int stl_shamap_tree_apply_nodes(stl_shamap_tree *t, const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *op,
+                                size_t n, uint8_t root[32], uint32_t counts[8], const stl_shamap_nodes_out *out);
+
 #ifdef __cplusplus
 }
 #endif

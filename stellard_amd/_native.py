@@ -88,6 +88,10 @@ STL_SIGCACHE_WAYS = 4
 # SHAMap root (stl_shamap_root*)
 STL_SHAMAP_MAX_ITEMS = 16777216
 
+# SHAMap inner nodes (stl_shamap_nodes*, stl_shamap_tree_apply_nodes*)
+STL_SHAMAP_MAX_NODES = 0xFFFFFFC0
+STL_SHAMAP_NODE_BODY_BYTES = 512
+
 # arithmetic self-test (stl_debug_selftest_*; row formats in csrc/stl_selftest.h)
 STL_SELFTEST_OPS = 47
 STL_SELFTEST_GROUP_OPS = 7
@@ -202,7 +206,20 @@ SYMBOLS = [
     ("stl_shamap_tree_apply", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P]),
     ("stl_shamap_tree_root_device", ctypes.c_int, [_P, _U8P, _P]),
     ("stl_shamap_tree_export_device", ctypes.c_int, [_P, _U8P, _U8P, ctypes.c_size_t, _P, _P]),
+    ("stl_shamap_nodes_device", ctypes.c_int, [_U8P, _U8P, _P, ctypes.c_size_t, _U8P, _P, _P, _P]),
+    ("stl_shamap_nodes", ctypes.c_int, [_U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_tree_apply_nodes_device", ctypes.c_int,
+     [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P, _P]),
+    ("stl_shamap_tree_apply_nodes", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
 ]
+
+
+class ShamapNodesOut(ctypes.Structure):
+    """stl_shamap_nodes_out (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_nodes", ctypes.c_uint32), ("hash", ctypes.c_void_p),
+                ("body", ctypes.c_void_p), ("id", ctypes.c_void_p), ("meta", ctypes.c_void_p),
+                ("count", ctypes.c_void_p)]
+
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
 STL_VERDICT_REJECT, STL_VERDICT_ACCEPT, STL_VERDICT_DEFER = 0, 1, 2

@@ -17,6 +17,8 @@
                                  node rule and inner-node hash
   tests/native/libhostemu_shamap_tree.so  the resident SHAMap's bucket, delta,
                                  position and top rules and its staged apply
+  tests/native/libhostemu_shamap_nodes.so  the stored inner nodes' masking,
+                                 leaf and top rules and both staged calls
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -147,6 +149,8 @@ SMALL_HARNESSES = {
     "shamap": ("hostemu_shamap.cpp", ("stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
     "shamap_tree": ("hostemu_shamap_tree.cpp", ("stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
                                                 "stl_fe25519.h")),
+    "shamap_nodes": ("hostemu_shamap_nodes.cpp", ("stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
+                                                  "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -200,6 +204,10 @@ def build_hostemu_shamap_tree(force=False):
     return _build_small("shamap_tree", force)
 
 
+def build_hostemu_shamap_nodes(force=False):
+    return _build_small("shamap_nodes", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -223,7 +231,8 @@ def main(argv=None):
                 ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force),
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
-                ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force)]
+                ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force),
+                ex.submit(build_hostemu_shamap_nodes, force)]
         for j in jobs:
             j.result()
     build_oracle()

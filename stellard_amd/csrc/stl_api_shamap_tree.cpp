@@ -1,5 +1,6 @@
 // stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
-// ledger's changes): the stl_shamap_tree_* entry points of include/stl.h;
+// ledger's changes, and the inner nodes an apply makes new): the
+// stl_shamap_tree_* entry points of include/stl.h;
 // kernels: stl_shamap_tree.hip, and the sort and level kernels of stl_shamap.hip.
 #include "stl_host.h"
 #include "stl_shamap.h"
@@ -62,7 +63,8 @@ int check_apply_args(const stl_shamap_tree* t, const void* key, const void* leaf
 // enqueued, and waited for only when the host's bound of the count no longer
 // admits the batch.  Nothing of *t changes here; the caller commits.
 int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf, const uint8_t* d_op,
-                 size_t n, uint8_t* d_root, uint32_t* d_counts, hipStream_t s, uint32_t* bound) {
+                 size_t n, uint8_t* d_root, uint32_t* d_counts, hipStream_t s, uint32_t* bound,
+                 const ShamapEmit* emit = nullptr) {
   const bool fits = (uint64_t)t->bound + n <= t->capacity;
   size_t temp = 0, temp_buckets = 0;
   STL_TRY(stl::shamap_temp_bytes(n, &temp));
@@ -102,7 +104,7 @@ int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint
   } else {
     *bound = t->bound + (uint32_t)n;
   }
-  STL_TRY(stl::launch_shamap_tree_merge(a, (uint32_t)n, d_root, d_counts, fault_now, phase_clock(d), s));
+  STL_TRY(stl::launch_shamap_tree_merge(a, (uint32_t)n, d_root, d_counts, fault_now, phase_clock(d), s, emit));
   return STL_OK;
 }
 
@@ -215,6 +217,64 @@ int stl_shamap_tree_apply(stl_shamap_tree* t, const uint8_t* key, const uint8_t*
     call.download(root, d.txid, 32);
     call.download(counts, d.status, 32);
     return STL_OK;
+  });
+  if (rc == STL_OK && n) tree_commit(t, bound);  // only once the results are back
+  return rc;
+}
+
+int stl_shamap_tree_apply_nodes_device(stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf_hash,
+                                       const uint8_t* d_op, size_t n, uint8_t* d_root, uint32_t* d_counts,
+                                       const stl_shamap_nodes_out* out, void* stream) {
+  STL_RC(check_apply_args(t, d_key, d_leaf_hash, n, d_root, d_counts, true));
+  STL_RC(check_nodes_out(out, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  if (n > t->capacity) return STL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, s, out->count));
+    return STL_OK;
+  }
+  const ShamapEmit emit = emit_of(*out);
+  uint32_t bound = 0;
+  STL_RC(tree_enqueue(*d, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, s, &bound, &emit));
+  tree_commit(t, bound);
+  return STL_OK;
+}
+
+int stl_shamap_tree_apply_nodes(stl_shamap_tree* t, const uint8_t* key, const uint8_t* leaf_hash, const uint8_t* op,
+                                size_t n, uint8_t root[32], uint32_t counts[8], const stl_shamap_nodes_out* out) {
+  STL_RC(check_apply_args(t, key, leaf_hash, n, root, counts, false));
+  STL_RC(check_nodes_out(out, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(g_trees.for_call(t, &dp));
+  if (n > t->capacity) return STL_EINVAL;
+  uint32_t bound = 0;
+  HostCall call("stl_shamap_tree_apply_nodes", n, *dp);
+  const int rc = call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(d.txid.ensure(32));
+    STL_RC(d.status.ensure(32));
+    NodeStage stage;
+    STL_RC(stage.ensure(d, *out));
+    uint8_t* d_root = static_cast<uint8_t*>(d.txid.p);
+    uint32_t* d_counts = static_cast<uint32_t*>(d.status.p);
+    if (n == 0) {
+      STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, d.stream, stage.emit.count));
+    } else {
+      STL_RC(call.upload(d.pk, key, n * 32));
+      if (leaf_hash) STL_RC(call.upload(d.msg, leaf_hash, n * 32));
+      if (op) STL_RC(call.upload(d.sig, op, n));
+      STL_RC(tree_enqueue(d, t, static_cast<const uint8_t*>(d.pk.p),
+                          leaf_hash ? static_cast<const uint8_t*>(d.msg.p) : nullptr,
+                          op ? static_cast<const uint8_t*>(d.sig.p) : nullptr, n, d_root, d_counts, d.stream, &bound,
+                          &stage.emit));
+    }
+    call.download(root, d.txid, 32);
+    call.download(counts, d.status, 32);
+    return stage.fetch(call, *out);
   });
   if (rc == STL_OK && n) tree_commit(t, bound);  // only once the results are back
   return rc;

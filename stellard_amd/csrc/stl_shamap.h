@@ -17,6 +17,21 @@ namespace stl {
 constexpr size_t kShamapRowBytes = 8 + 8 + 4 + 4 + 1 + 32 + 32;
 constexpr size_t kShamapHeaderBytes = 512;  // 64 nodes-per-depth words, distinct and selected counts
 constexpr uint32_t kShamapHdrDistinct = 64;  // the header word that holds the number of sorted distinct keys
+constexpr uint32_t kShamapHdrEmitted = 66;   // ... and the one that numbers the stored nodes (stl_shamap_nodes*)
+
+// Where a call stores its inner nodes (stl_shamap_nodes_out of include/stl.h,
+// device pointers): row i of hash (32 B), body (512 B), id (32 B, or null) and
+// meta (a word, or null), i < max_nodes; hash, body and id 16-byte aligned.
+// Rows are numbered by adding to one header word, so their order is free.
+constexpr size_t kShamapNodeRowBytes = 32 + 512 + 32 + 4;
+struct ShamapEmit {
+  uint8_t* hash;
+  uint8_t* body;
+  uint8_t* id;
+  uint32_t* meta;
+  uint32_t max_nodes;
+  uint32_t* count;  // the caller's count word: written by the finish launch alone
+};
 
 // What the radix sort and the scan of n rows want as temporary storage (the
 // larger of their needs; no device work), and the whole workspace of a call.
@@ -30,10 +45,11 @@ size_t shamap_workspace_bytes(size_t n, size_t temp_bytes);
 // last launch alone.  fault (or null): asked before every HIP call; true makes
 // the call fail there (stl_debug_fault_after).  clock (or null): marked before
 // the first launch (0) and after the sort (1), the heads and neighbours (2),
-// the levels (3) and the finish (4).  n >= 1.
+// the levels (3) and the finish (4).  n >= 1.  emit (or null): every inner node
+// is also stored there, by the emitting instantiation of the level kernel.
 hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uint64_t* select, uint32_t n,
                               uint8_t* root, uint32_t* counts, void* ws, size_t temp_bytes, bool (*fault)(),
-                              const PhaseClock* clock, hipStream_t stream);
+                              const PhaseClock* clock, hipStream_t stream, const ShamapEmit* emit = nullptr);
 
 // ---- the parts the resident tree (stl_shamap_tree.hip) runs on arrays of its own ----
 // The same sort passes over n keys in a workspace of shamap_workspace_bytes(n,
@@ -60,8 +76,28 @@ hipError_t shamap_exclusive_scan(void* temp, size_t temp_bytes, const uint32_t* 
 // zero but for hdr[kShamapHdrDistinct] = the number of keys, read on the
 // device); n: a host-known bound of that number, which sizes the grids and the
 // neighbour bytes l.  Afterwards the slot of the first key of every node at
-// depth d_last holds that node's hash.
+// depth d_last holds that node's hash.  emit (or null): the nodes of those
+// depths are stored, numbered by hdr[kShamapHdrEmitted]; emit->count is not written.
 hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
-                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream);
+                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream,
+                                const ShamapEmit* emit = nullptr);
 
+}  // namespace stl
+
+// ---- host side of the node-storing calls (stl_api_shamap.cpp), shared with stl_api_shamap_tree.cpp ----
+struct stl_shamap_nodes_out;
+namespace stl {
+struct Device;
+struct HostCall;
+// The argument checks of a stl_shamap_nodes_out: STL_OK or STL_EINVAL, no device work.
+int check_nodes_out(const stl_shamap_nodes_out* out, bool device_form);
+ShamapEmit emit_of(const stl_shamap_nodes_out& out);
+// A host form's staging of the node arrays on the device (under the device's
+// mutex: the device's own buffers, grown to max_nodes rows), and their way back:
+// fetch waits for the count and names min(count, max_nodes) rows as the call's outputs.
+struct NodeStage {
+  ShamapEmit emit{};
+  int ensure(Device& d, const stl_shamap_nodes_out& out);
+  int fetch(HostCall& call, const stl_shamap_nodes_out& out);
+};
 }  // namespace stl

@@ -165,11 +165,34 @@ __global__ __launch_bounds__(kSmBlock) void shamap_neighbour_kernel(const uint8_
   if (threadIdx.x < kShamapDepths && hist[threadIdx.x]) atomicAdd(&hdr[threadIdx.x], hist[threadIdx.x]);
 }
 
+// What the emitting level kernel is given: ShamapEmit's arrays and the header
+// word the rows are numbered from (never one the kernel reads through hdr).
+struct SmEmit {
+  uint8_t* hash;
+  uint8_t* body;
+  uint8_t* id;
+  uint32_t* meta;
+  uint32_t max_nodes;
+  uint32_t* counter;
+};
+
 // Gathers and hashes the `count` nodes listed in node_pos (the whole workgroup).
+// kEmit: the nodes are also stored (ShamapEmit): the tile takes `count` row
+// numbers from the call's counter word with one add, the gather lanes note which
+// branches are leaves, and after the hash the tile goes out -- the bodies
+// straight from the LDS records, 16 bytes per lane, consecutive lanes on
+// consecutive pieces of a row, so a wave writes whole 128-byte lines.  Every
+// store is guarded by the row number being below max_nodes.
+template <bool kEmit>
 __device__ __forceinline__ void shamap_flush(uint32_t* rec, const uint32_t* node_pos, uint32_t count, uint32_t m,
-                                             const uint8_t* __restrict__ skey, uint8_t* slot, uint32_t d) {
+                                             const uint8_t* __restrict__ skey, uint8_t* slot, uint32_t d,
+                                             const int8_t* __restrict__ l, const SmEmit& em, uint32_t* node_leaf,
+                                             uint32_t* tile_base) {
   const uint32_t tid = threadIdx.x;
   __syncthreads();  // node_pos is written
+  if constexpr (kEmit) {
+    if (tid == 0) *tile_base = atomicAdd(em.counter, count);
+  }
   // gather: 16 lanes per node, one per branch
   const uint32_t c = tid & 15u;
   for (uint32_t k = tid >> 4; k < count; k += kSmBlock / 16) {
@@ -182,6 +205,11 @@ __device__ __forceinline__ void shamap_flush(uint32_t* rec, const uint32_t* node
       h0 = q[0];
       h1 = q[1];
     }
+    if constexpr (kEmit) {
+      // the 16 lanes of a node sit side by side in their wave and leave the loop together
+      const uint64_t leaves = __ballot(p < e && shamap_branch_is_leaf(l, p, e, d));
+      if (c == 0) node_leaf[k] = (uint32_t)(leaves >> (tid & 48u)) & 0xffffu;
+    }
     uint32_t* r = rec + k * kShamapRecordWords;
     if (c == 0) r[0] = kShamapInnerPrefix;
     r += 1 + 8 * c;
@@ -193,7 +221,31 @@ __device__ __forceinline__ void shamap_flush(uint32_t* rec, const uint32_t* node
   if (tid < count) {
     uint32_t out[8];
     shamap_inner_hash(out, rec + tid * kShamapRecordWords);
-    sm_st8(slot, node_pos[tid], out);
+    const uint32_t a = node_pos[tid];
+    sm_st8(slot, a, out);
+    if constexpr (kEmit) {
+      const uint32_t row = *tile_base + tid;
+      if (row < em.max_nodes) {
+        sm_st8(em.hash, row, out);
+        if (em.id) {
+          uint32_t key[8], id[8];
+          shamap_load_key(key, skey, a);
+          shamap_mask_key(id, key, d);
+          sm_st8(em.id, row, id);
+        }
+        if (em.meta) em.meta[row] = shamap_node_meta(d, node_leaf[tid]);
+      }
+    }
+  }
+  if constexpr (kEmit) {
+    // the bodies: piece q is 16 bytes, 32 pieces to a row
+    const uint32_t base = *tile_base;
+    for (uint32_t q = tid; q < 32u * count; q += kSmBlock) {
+      const uint32_t k = q >> 5, part = q & 31u;
+      if (base + k >= em.max_nodes) continue;
+      const uint32_t* r = rec + k * kShamapRecordWords + 1 + 4 * part;
+      *reinterpret_cast<uint4*>(em.body + 512 * (size_t)(base + k) + 16 * part) = make_uint4(r[0], r[1], r[2], r[3]);
+    }
   }
   __syncthreads();  // rec and node_pos may be reused
 }
@@ -205,13 +257,16 @@ __device__ __forceinline__ void shamap_flush(uint32_t* rec, const uint32_t* node
 // that a sparse depth (a few nodes per thousand positions: clustered keys)
 // still fills the hashing lanes, while at least kSmSpansWanted workgroups
 // share the depth.
+template <bool kEmit>
 __global__ __launch_bounds__(kSmBlock) void shamap_level_kernel(const uint32_t* __restrict__ hdr,
                                                                 const int8_t* __restrict__ l,
                                                                 const uint8_t* __restrict__ skey, uint8_t* slot,
-                                                                uint32_t d) {
+                                                                uint32_t d, SmEmit em) {
   __shared__ uint32_t rec[kSmTileNodes * kShamapRecordWords];
   __shared__ uint32_t node_pos[kSmTileNodes];
   __shared__ uint32_t wave_nodes[kSmBlock / 64];
+  __shared__ uint32_t node_leaf[kEmit ? kSmTileNodes : 1];
+  __shared__ uint32_t tile_base[1];
   const uint32_t nodes = hdr[d];
   if (nodes == 0) return;  // uniform: no node at this depth
   const uint32_t m = hdr[kHdrDistinct];
@@ -241,7 +296,7 @@ __global__ __launch_bounds__(kSmBlock) void shamap_level_kernel(const uint32_t* 
         here += wave_nodes[v];
       }
       if (count + here > kSmTileNodes) {  // uniform
-        shamap_flush(rec, node_pos, count, m, skey, slot, d);
+        shamap_flush<kEmit>(rec, node_pos, count, m, skey, slot, d, l, em, node_leaf, tile_base);
         count = 0;
       }
       if (starts) {
@@ -252,17 +307,19 @@ __global__ __launch_bounds__(kSmBlock) void shamap_level_kernel(const uint32_t* 
       if (count > kSmTileNodes) count = kSmTileNodes;  // never
       __syncthreads();  // wave_nodes is reused by the next chunk
     }
-    if (count) shamap_flush(rec, node_pos, count, m, skey, slot, d);
+    if (count) shamap_flush<kEmit>(rec, node_pos, count, m, skey, slot, d, l, em, node_leaf, tile_base);
   }
 }
 
-// root = slot 0 (zeros for the empty map); counts.
+// root = slot 0 (zeros for the empty map); counts; the number of stored nodes (or null).
 __global__ __launch_bounds__(64) void shamap_finish_kernel(const uint32_t* __restrict__ hdr,
                                                            const uint8_t* __restrict__ slot,
                                                            uint32_t* __restrict__ root,
-                                                           uint32_t* __restrict__ counts) {
+                                                           uint32_t* __restrict__ counts,
+                                                           uint32_t* __restrict__ emitted) {
   const uint32_t t = threadIdx.x;
   const uint32_t m = hdr[kHdrDistinct];
+  if (t == 0 && emitted) *emitted = hdr[kShamapHdrEmitted];
   if (t < 8) root[t] = m ? reinterpret_cast<const uint32_t*>(slot)[t] : 0u;
   const uint32_t nodes = hdr[t];
   // the sum over the depths and the deepest depth in use, by wave reduction
@@ -351,6 +408,27 @@ size_t shamap_workspace_bytes(size_t n, size_t temp_bytes) { return ShamapWs(nul
     if (e_ != hipSuccess) return e_;                                    \
   } while (0)
 
+static bool shamap_emit_ok(const ShamapEmit& e) {
+  return e.hash && e.body && !(((uintptr_t)e.hash | (uintptr_t)e.body | (uintptr_t)e.id) & 15u) &&
+         !((uintptr_t)e.meta & 3u);
+}
+
+// The level kernel for depths d_first down to d_last, one launch each: the
+// emitting instantiation when the nodes are stored, else the plain one.
+static hipError_t shamap_level_launches(uint32_t* hdr, const int8_t* l, const uint8_t* skey, uint8_t* slot,
+                                        uint32_t grid, uint32_t d_first, uint32_t d_last, const ShamapEmit* emit,
+                                        bool (*fault)(), hipStream_t stream) {
+  SmEmit em{};
+  if (emit) em = SmEmit{emit->hash, emit->body, emit->id, emit->meta, emit->max_nodes, hdr + kShamapHdrEmitted};
+  for (int d = (int)d_first; d >= (int)d_last; --d) {
+    if (emit)
+      SM_LAUNCH(shamap_level_kernel<true>, grid, kSmBlock, hdr, l, skey, slot, (uint32_t)d, em);
+    else
+      SM_LAUNCH(shamap_level_kernel<false>, grid, kSmBlock, hdr, l, skey, slot, (uint32_t)d, em);
+  }
+  return hipSuccess;
+}
+
 // The four stable radix passes over (sort word, row), least significant word first.
 static hipError_t shamap_sort_passes(const uint8_t* key, uint32_t n, const ShamapWs& w, size_t temp_bytes,
                                      rocprim::double_buffer<uint64_t>& k64, rocprim::double_buffer<uint32_t>& v,
@@ -367,8 +445,9 @@ static hipError_t shamap_sort_passes(const uint8_t* key, uint32_t n, const Shama
 
 hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uint64_t* select, uint32_t n,
                               uint8_t* root, uint32_t* counts, void* ws, size_t temp_bytes, bool (*fault)(),
-                              const PhaseClock* clock, hipStream_t stream) {
+                              const PhaseClock* clock, hipStream_t stream, const ShamapEmit* emit) {
   if (n == 0 || !key || !root || !ws) return hipErrorInvalidValue;
+  if (emit && !shamap_emit_ok(*emit)) return hipErrorInvalidValue;
   if (((uintptr_t)key & 15u) || ((uintptr_t)leaf & 15u) || ((uintptr_t)root & 3u) || ((uintptr_t)ws & 255u))
     return hipErrorInvalidValue;
   const ShamapWs w(ws, n, temp_bytes);
@@ -402,11 +481,14 @@ hipError_t launch_shamap_root(const uint8_t* key, const uint8_t* leaf, const uin
   if (clock) clock->mark(clock->ctx, stream, 2);
   // 4. levels
   const uint32_t lg = g < kSmLevelGrid ? g : kSmLevelGrid;
-  for (int d = (int)kShamapDepths - 1; d >= 0; --d)
-    SM_LAUNCH(shamap_level_kernel, lg, kSmBlock, w.hdr, w.l, w.skey, w.slot, (uint32_t)d);
+  {
+    const hipError_t e = shamap_level_launches(w.hdr, w.l, w.skey, w.slot, lg, kShamapDepths - 1, 0, emit, fault, stream);
+    if (e != hipSuccess) return e;
+  }
   if (clock) clock->mark(clock->ctx, stream, 3);
   // 5. finish
-  SM_LAUNCH(shamap_finish_kernel, 1, 64, w.hdr, w.slot, reinterpret_cast<uint32_t*>(root), counts);
+  SM_LAUNCH(shamap_finish_kernel, 1, 64, w.hdr, w.slot, reinterpret_cast<uint32_t*>(root), counts,
+            emit ? emit->count : static_cast<uint32_t*>(nullptr));
   if (clock) clock->mark(clock->ctx, stream, 4);
   return hipSuccess;
 }
@@ -436,15 +518,15 @@ hipError_t shamap_exclusive_scan(void* temp, size_t temp_bytes, const uint32_t* 
 }
 
 hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
-                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream) {
+                                uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream,
+                                const ShamapEmit* emit) {
   if (n == 0 || !hdr || !l || !skey || !slot || d_first >= kShamapDepths || d_last > d_first)
     return hipErrorInvalidValue;
+  if (emit && !shamap_emit_ok(*emit)) return hipErrorInvalidValue;
   const uint32_t g = grid_of(n);
   SM_LAUNCH(shamap_neighbour_kernel, g, kSmBlock, skey, n, l, hdr);
   const uint32_t lg = g < kSmLevelGrid ? g : kSmLevelGrid;
-  for (int d = (int)d_first; d >= (int)d_last; --d)
-    SM_LAUNCH(shamap_level_kernel, lg, kSmBlock, hdr, l, skey, slot, (uint32_t)d);
-  return hipSuccess;
+  return shamap_level_launches(hdr, l, skey, slot, lg, d_first, d_last, emit, fault, stream);
 }
 
 }  // namespace stl

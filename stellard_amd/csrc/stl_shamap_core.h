@@ -138,6 +138,30 @@ STL_HD uint32_t shamap_branch_first(const uint8_t* skey, uint32_t a, uint32_t e,
   return (p0 < e && shamap_nibble_bytes(skey + 32 * (size_t)p0, d) == c) ? p0 : e;
 }
 
+// ---- what a stored inner node carries besides its hash (stl_shamap_nodes*) ----
+// A node's ID: its first key with everything past the first d nibbles cleared
+// (SHAMapNodeID's masked key), as memory-order dwords.
+STL_HD void shamap_mask_key(uint32_t out[kShamapKeyWords], const uint32_t key[kShamapKeyWords], uint32_t d) {
+  for (uint32_t i = 0; i < kShamapKeyWords; ++i) {
+    const uint32_t keep = d <= 8u * i ? 0u : (d - 8u * i >= 8u ? 8u : d - 8u * i);  // nibbles of dword i that stay
+    const uint32_t bytes = keep >> 1;
+    uint32_t mask = bytes >= 4u ? 0xffffffffu : ((1u << (8u * bytes)) - 1u);
+    if (keep & 1u) mask |= 0xf0u << (8u * bytes);
+    out[i] = key[i] & mask;
+  }
+}
+
+// The leaf rule: branch c of the node at depth d with range [a, e) holds one key
+// (its hash is that key's leaf hash, not an inner node's) exactly when the
+// branch's first position p (< e) is the range's last or the key after it
+// parts from it at nibble d or before.  l: the neighbour bytes.
+STL_HD bool shamap_branch_is_leaf(const int8_t* l, uint32_t p, uint32_t e, uint32_t d) {
+  return p + 1 == e || (int32_t)l[p] <= (int32_t)d;
+}
+
+// The meta word of a stored node: bits 0-7 its depth, bit 16 + c: branch c is a leaf.
+STL_HD uint32_t shamap_node_meta(uint32_t d, uint32_t leaf_mask) { return (d & 0xffu) | ((leaf_mask & 0xffffu) << 16); }
+
 // SHA512Half of an inner node's record: rec[0] = kShamapInnerPrefix, rec[1 + 8 c
 // .. 8 + 8 c] = the hash of branch c (zeros: empty), each as memory-order
 // dwords -> out, 8 memory-order dwords.  Five compressions.

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "stl_kernels.h"
+#include "stl_shamap.h"
 
 namespace stl {
 
@@ -62,10 +63,15 @@ struct TreeApply {
 hipError_t launch_shamap_tree_locate(const TreeApply& a, const uint8_t* key, const uint8_t* leaf, const uint8_t* op,
                                      uint32_t n, bool (*fault)(), const PhaseClock* clock, hipStream_t stream);
 const uint32_t* shamap_tree_change_counts(void* fixed);
+// emit (or null): the merge also stores the new tree's inner nodes of the
+// dirty buckets (the scratch's level launches, emitting) and of the top
+// prefixes above them, and its last launch writes their number to emit->count.
 hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* root, uint32_t* counts, bool (*fault)(),
-                                    const PhaseClock* clock, hipStream_t stream);
-// root <- the generation's root; counts (or null) <- its item count and seven zeros.
-hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* counts, hipStream_t stream);
+                                    const PhaseClock* clock, hipStream_t stream, const ShamapEmit* emit = nullptr);
+// root <- the generation's root; counts (or null) <- its item count and seven
+// zeros; node_count (or null) <- zero: no node is stored.
+hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* counts, hipStream_t stream,
+                                     uint32_t* node_count = nullptr);
 // The generation's sorted content -> key / leaf (either may be null) of `rows`
 // rows, items_bound <= rows; *items (or null) <- the count.
 hipError_t launch_shamap_tree_export(const TreeGen& g, uint32_t items_bound, uint8_t* key, uint8_t* leaf,

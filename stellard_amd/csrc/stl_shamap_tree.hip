@@ -54,7 +54,7 @@ uint32_t grid_of(uint32_t n) { return (n + kTrBlock - 1) / kTrBlock; }
 
 // The work areas' parts, in order.
 struct TreeFixed {
-  uint32_t *wh, *dirty, *lb, *sz, *off, *topcnt, *toph;
+  uint32_t *wh, *dirty, *lb, *sz, *off, *topcnt, *toph, *topdirty;
   size_t bytes;
   explicit TreeFixed(void* base) {
     uint8_t* p = static_cast<uint8_t*>(base);
@@ -71,6 +71,7 @@ struct TreeFixed {
     off = take(4 * kTreeBuckets);
     topcnt = take(4 * kTreeTopValues);
     toph = take(32 * kTreeTopValues);
+    topdirty = take(4 * kTreeTopValues);  // a dirty bucket lies below the prefix (the storing apply alone)
     bytes = o;
   }
 };
@@ -306,23 +307,62 @@ __global__ __launch_bounds__(kTrBlock) void tree_bucket_kernel(const uint32_t* _
   tr_st8(reinterpret_cast<uint8_t*>(to_h), b, h);
 }
 
-// 6b. one depth of the top: `nodes` values from 16 children each.
+// What the storing top kernel is given besides the values: the children's
+// "a dirty bucket lies below" words and where its own go (null at the root),
+// the prefixes' length, ShamapEmit's arrays and the word the rows are numbered from.
+struct TopEmit {
+  const uint32_t* child_dirty;
+  uint32_t* out_dirty;
+  uint32_t depth;
+  uint8_t* hash;
+  uint8_t* body;
+  uint8_t* id;
+  uint32_t* meta;
+  uint32_t max_nodes;
+  uint32_t* counter;
+};
+
+// 6b. one depth of the top: `nodes` values from 16 children each.  kEmit: a
+// prefix that is an inner node above a dirty bucket is also stored, one row
+// number per node from the counter the level kernel has used; every store is
+// guarded by the row number being below max_nodes.
+template <bool kEmit>
 __global__ __launch_bounds__(64) void tree_top_kernel(const uint32_t* __restrict__ child_cnt,
                                                       const uint32_t* __restrict__ child_h, uint32_t nodes, bool root,
-                                                      uint32_t* __restrict__ out_cnt, uint32_t* __restrict__ out_h) {
+                                                      uint32_t* __restrict__ out_cnt, uint32_t* __restrict__ out_h,
+                                                      TopEmit em) {
   const uint32_t t = blockIdx.x * 64 + threadIdx.x;
   if (t >= nodes) return;
   uint32_t h[8];
   const uint32_t c = shamap_tree_top_value(child_cnt + 16 * t, child_h + 128 * (size_t)t, root, h);
   if (out_cnt) out_cnt[t] = c;
   for (uint32_t i = 0; i < 8; ++i) out_h[8 * t + i] = h[i];
+  if constexpr (kEmit) {
+    uint32_t below = 0;
+    for (uint32_t k = 0; k < kShamapBranches; ++k) below |= em.child_dirty[16 * t + k];
+    if (em.out_dirty) em.out_dirty[t] = below ? 1u : 0u;
+    if (!shamap_tree_top_emits(c, root, below != 0)) return;
+    const uint32_t row = atomicAdd(em.counter, 1u);
+    if (row >= em.max_nodes) return;
+    uint32_t body[16 * kShamapKeyWords], id[8];
+    const uint32_t leaf = shamap_tree_top_node(child_cnt + 16 * t, child_h + 128 * (size_t)t, em.depth, t, body, id);
+    tr_st8(em.hash, row, h);
+    uint4* q = reinterpret_cast<uint4*>(em.body + 512 * (size_t)row);
+    for (uint32_t i = 0; i < 32; ++i) q[i] = make_uint4(body[4 * i], body[4 * i + 1], body[4 * i + 2], body[4 * i + 3]);
+    if (em.id) tr_st8(em.id, row, id);
+    if (em.meta) em.meta[row] = shamap_node_meta(em.depth, leaf);
+  }
 }
 
-// 7. root and counts.
+// 7. root and counts; the number of stored nodes (emitted: its counter, or null
+// for none) -> node_count (or null).
 __global__ __launch_bounds__(64) void tree_finish_kernel(const uint32_t* __restrict__ meta,
                                                          const uint32_t* __restrict__ wh, uint32_t n,
-                                                         uint32_t* __restrict__ root, uint32_t* __restrict__ counts) {
+                                                         uint32_t* __restrict__ root, uint32_t* __restrict__ counts,
+                                                         const uint32_t* __restrict__ emitted,
+                                                         uint32_t* __restrict__ node_count) {
   const uint32_t t = threadIdx.x;
+  if (t == 0 && node_count) *node_count = emitted ? *emitted : 0u;
   if (t < 8) root[t] = meta[kTreeMetaRoot + t];
   if (t == 0 && counts) {
     counts[0] = meta[0];
@@ -413,7 +453,7 @@ hipError_t launch_shamap_tree_locate(const TreeApply& a, const uint8_t* key, con
 const uint32_t* shamap_tree_change_counts(void* fixed) { return TreeFixed(fixed).wh; }
 
 hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* root, uint32_t* counts, bool (*fault)(),
-                                    const PhaseClock* clock, hipStream_t stream) {
+                                    const PhaseClock* clock, hipStream_t stream, const ShamapEmit* emit) {
   if (n == 0 || !root || !a.fixed || !a.batch || !a.scratch || !a.sort_ws) return hipErrorInvalidValue;
   if (((uintptr_t)root & 3u) || ((uintptr_t)counts & 3u)) return hipErrorInvalidValue;
   if (a.capacity == 0 || a.items_bound > a.capacity || a.after_bound > a.capacity || a.after_bound == 0)
@@ -439,27 +479,50 @@ hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* roo
   TR_TRY(hipMemsetAsync(s.hdr, 0, kShamapHeaderBytes, stream));
   TR_LAUNCH(tree_gather_kernel, grid_of(after), kTrBlock, a.to.key, a.to.leaf, f.lb, f.sz, f.off, cap, s.hdr, s.skey,
             s.slot, f.wh);
-  TR_RC(launch_shamap_levels(s.hdr, s.l, s.skey, s.slot, after, kShamapDepths - 1, kTreeBucketDepth, fault, stream));
+  TR_RC(launch_shamap_levels(s.hdr, s.l, s.skey, s.slot, after, kShamapDepths - 1, kTreeBucketDepth, fault, stream,
+                             emit));
   if (clock) clock->mark(clock->ctx, stream, 3);
   // 6. bucket values and top
   TR_LAUNCH(tree_bucket_kernel, gb, kTrBlock, f.dirty, f.sz, f.off, s.slot, cap, a.from.bcnt, a.from.bh, a.to.bcnt,
             a.to.bh);
-  TR_LAUNCH(tree_top_kernel, 4096 / 64, 64, a.to.bcnt, a.to.bh, 4096u, false, f.topcnt, f.toph);
-  TR_LAUNCH(tree_top_kernel, 256 / 64, 64, f.topcnt, f.toph, 256u, false, f.topcnt + 4096, f.toph + 8 * 4096);
-  TR_LAUNCH(tree_top_kernel, 1, 64, f.topcnt + 4096, f.toph + 8 * 4096, 16u, false, f.topcnt + 4096 + 256,
-            f.toph + 8 * (4096 + 256));
-  TR_LAUNCH(tree_top_kernel, 1, 64, f.topcnt + 4096 + 256, f.toph + 8 * (4096 + 256), 1u, true,
-            static_cast<uint32_t*>(nullptr), a.to.meta + kTreeMetaRoot);
+  uint32_t* const no_words = nullptr;
+  if (emit) {
+    // the same four launches, storing: the row numbers go on from where the scratch's level launches stopped
+    TopEmit te{f.dirty, f.topdirty, 3u, emit->hash, emit->body, emit->id, emit->meta, emit->max_nodes,
+               s.hdr + kShamapHdrEmitted};
+    TR_LAUNCH(tree_top_kernel<true>, 4096 / 64, 64, a.to.bcnt, a.to.bh, 4096u, false, f.topcnt, f.toph, te);
+    te.child_dirty = f.topdirty, te.out_dirty = f.topdirty + 4096, te.depth = 2u;
+    TR_LAUNCH(tree_top_kernel<true>, 256 / 64, 64, f.topcnt, f.toph, 256u, false, f.topcnt + 4096, f.toph + 8 * 4096,
+              te);
+    te.child_dirty = f.topdirty + 4096, te.out_dirty = f.topdirty + 4096 + 256, te.depth = 1u;
+    TR_LAUNCH(tree_top_kernel<true>, 1, 64, f.topcnt + 4096, f.toph + 8 * 4096, 16u, false, f.topcnt + 4096 + 256,
+              f.toph + 8 * (4096 + 256), te);
+    te.child_dirty = f.topdirty + 4096 + 256, te.out_dirty = nullptr, te.depth = 0u;
+    TR_LAUNCH(tree_top_kernel<true>, 1, 64, f.topcnt + 4096 + 256, f.toph + 8 * (4096 + 256), 1u, true, no_words,
+              a.to.meta + kTreeMetaRoot, te);
+  } else {
+    const TopEmit te{};
+    TR_LAUNCH(tree_top_kernel<false>, 4096 / 64, 64, a.to.bcnt, a.to.bh, 4096u, false, f.topcnt, f.toph, te);
+    TR_LAUNCH(tree_top_kernel<false>, 256 / 64, 64, f.topcnt, f.toph, 256u, false, f.topcnt + 4096, f.toph + 8 * 4096,
+              te);
+    TR_LAUNCH(tree_top_kernel<false>, 1, 64, f.topcnt + 4096, f.toph + 8 * 4096, 16u, false, f.topcnt + 4096 + 256,
+              f.toph + 8 * (4096 + 256), te);
+    TR_LAUNCH(tree_top_kernel<false>, 1, 64, f.topcnt + 4096 + 256, f.toph + 8 * (4096 + 256), 1u, true, no_words,
+              a.to.meta + kTreeMetaRoot, te);
+  }
   // 7. finish
-  TR_LAUNCH(tree_finish_kernel, 1, 64, a.to.meta, f.wh, n, reinterpret_cast<uint32_t*>(root), counts);
+  TR_LAUNCH(tree_finish_kernel, 1, 64, a.to.meta, f.wh, n, reinterpret_cast<uint32_t*>(root), counts,
+            emit ? s.hdr + kShamapHdrEmitted : no_words, emit ? emit->count : no_words);
   if (clock) clock->mark(clock->ctx, stream, 4);
   return hipSuccess;
 }
 
-hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* counts, hipStream_t stream) {
-  if (!root || ((uintptr_t)root & 3u) || ((uintptr_t)counts & 3u)) return hipErrorInvalidValue;
+hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* counts, hipStream_t stream,
+                                     uint32_t* node_count) {
+  if (!root || ((uintptr_t)root & 3u) || ((uintptr_t)counts & 3u) || ((uintptr_t)node_count & 3u))
+    return hipErrorInvalidValue;
   hipLaunchKernelGGL(tree_finish_kernel, dim3(1), dim3(64), 0, stream, g.meta, static_cast<const uint32_t*>(nullptr), 0u,
-                     reinterpret_cast<uint32_t*>(root), counts);
+                     reinterpret_cast<uint32_t*>(root), counts, static_cast<const uint32_t*>(nullptr), node_count);
   return hipGetLastError();
 }
 

@@ -123,4 +123,28 @@ STL_HD uint32_t shamap_tree_top_value(const uint32_t* cnt, const uint32_t* h, bo
   return sum;
 }
 
+// ---- the top nodes an apply stores (stl_shamap_tree_apply_nodes*) ----
+// A prefix shorter than T is stored when a dirty bucket lies below it and it is
+// an inner node: it holds two keys or more, or it is the root and holds one.
+STL_HD bool shamap_tree_top_emits(uint32_t cnt, bool root, bool dirty_below) {
+  return dirty_below && (cnt >= 2u || (root && cnt >= 1u));
+}
+
+// The stored form of the prefix numbered t among those of length `depth`
+// (0 .. T - 1) from its 16 children's values: the body (the 16 hashes, zeros
+// for an empty child), the ID (the prefix's nibbles, then zeros) and the leaf
+// mask (the children that hold one key).
+STL_HD uint32_t shamap_tree_top_node(const uint32_t* cnt, const uint32_t* h, uint32_t depth, uint32_t t,
+                                     uint32_t body[16 * kShamapKeyWords], uint32_t id[kShamapKeyWords]) {
+  uint32_t leaf = 0;
+  for (uint32_t c = 0; c < kShamapBranches; ++c) {
+    if (cnt[c] == 1u) leaf |= 1u << c;
+    for (uint32_t i = 0; i < kShamapKeyWords; ++i) body[8 * c + i] = cnt[c] ? h[8 * c + i] : 0u;
+  }
+  const uint32_t v = depth ? t << (4u * (kTreeBucketDepth - depth)) : 0u;  // the prefix, left-aligned in 16 bits
+  id[0] = ((v >> 8) & 0xffu) | ((v & 0xffu) << 8);
+  for (uint32_t i = 1; i < kShamapKeyWords; ++i) id[i] = 0;
+  return leaf;
+}
+
 }  // namespace stl

@@ -961,6 +961,222 @@ class ShamapTree(_DeviceObject):
         return out_items
 
 
+    def apply_nodes_device(self, keys, leaf_hashes=None, ops=None, max_nodes=None, nodes=None, ids=True, meta=True,
+                           out_root=None, counts=True, stream=None):
+        """stl_shamap_tree_apply_nodes_device: ``apply_device``, and the new
+        tree's inner nodes of the dirty buckets and of the prefixes above them
+        -> (root, counts, nodes); ``nodes`` as ``shamap_nodes_device`` gives
+        it.  Asynchronous on ``stream``."""
+        import torch
+        if keys.dim() != 2:
+            raise ValueError("keys must be (n, 32) bytes")
+        n = keys.shape[0]
+        _check_hashes(n, keys=keys, leaf_hashes=leaf_hashes)
+        if ops is not None and (ops.dtype != torch.uint8 or tuple(ops.shape) != (n,)):
+            raise ValueError("ops must be uint8[n]")
+        if out_root is None:
+            out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
+        _check_hashes(1, out_root=out_root)
+        cnt = _node_counts(counts, 8, keys.device)
+        nodes = _device_nodes(nodes, max_nodes, ids, meta, keys.device)
+        for t in (keys, leaf_hashes, ops, out_root, cnt):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        out = nodes.struct()
+        N.check(N.load().stl_shamap_tree_apply_nodes_device(self._h, p(keys), p(leaf_hashes), p(ops), n, p(out_root),
+                                                            p(cnt), ctypes.byref(out), _stream_ptr(stream)),
+                "stl_shamap_tree_apply_nodes_device")
+        return out_root, cnt, nodes
+
+    def apply_nodes(self, keys, leaf_hashes=None, ops=None, max_nodes=0, ids=True, meta=True):
+        """stl_shamap_tree_apply_nodes: host memory, synchronous -> (32 root
+        bytes, [8 counts], nodes); ``nodes`` as ``shamap_nodes`` gives it."""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+            raise ValueError("keys must be (n, 32) uint8")
+        n = keys.shape[0]
+        if leaf_hashes is not None:
+            leaf_hashes = np.ascontiguousarray(leaf_hashes)
+            if leaf_hashes.dtype != np.uint8 or leaf_hashes.shape != (n, 32):
+                raise ValueError("leaf_hashes must be (n, 32) uint8")
+        if ops is not None:
+            ops = np.ascontiguousarray(ops)
+            if ops.dtype not in (np.uint8, np.bool_) or ops.shape != (n,):
+                raise ValueError("ops must be uint8[n] or bool[n]")
+            ops = ops.astype(np.uint8)
+        root = np.zeros(32, dtype=np.uint8)
+        cnt = np.zeros(8, dtype=np.uint32)
+        nodes = HostNodes(max_nodes, ids, meta)
+        out = nodes.struct()
+        N.check(N.load().stl_shamap_tree_apply_nodes(
+            self._h, _buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n else None,
+            _buf(ops) if ops is not None and n else None, n, _buf(root), _buf(cnt), ctypes.byref(out)),
+            "stl_shamap_tree_apply_nodes")
+        return root.tobytes(), [int(x) for x in cnt], nodes
+
+
+# ---- SHAMap inner nodes (stl_shamap_nodes*, stl_shamap_tree_apply_nodes*) ----
+
+SHAMAP_MAX_NODES = N.STL_SHAMAP_MAX_NODES
+SHAMAP_NODE_BODY_BYTES = N.STL_SHAMAP_NODE_BODY_BYTES
+
+
+def _nodes_struct(max_nodes, hash_, body, ids, meta, count):
+    p = lambda a: a if a is None or isinstance(a, int) else (  # noqa: E731
+        a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+    return N.ShamapNodesOut(ctypes.sizeof(N.ShamapNodesOut), max_nodes, p(hash_), p(body), p(ids), p(meta), p(count))
+
+
+class DeviceNodes:
+    """The inner nodes a device call stores, as CUDA tensors of ``max_nodes``
+    rows: hash (max_nodes, 32) uint8, body (max_nodes, 512) uint8, ids
+    (max_nodes, 32) uint8 or None, meta int32[max_nodes] or None, count
+    int32[1] -- the nodes the call produced, which may exceed max_nodes; rows
+    in no particular order.  Tensors given are written in place."""
+
+    def __init__(self, max_nodes, ids=True, meta=True, device="cuda", hash=None, body=None, count=None):  # noqa: A002
+        import torch
+        self.max_nodes = int(max_nodes)
+        if not 0 <= self.max_nodes <= SHAMAP_MAX_NODES:
+            raise ValueError("max_nodes must be in 0 .. SHAMAP_MAX_NODES")
+        rows = max(self.max_nodes, 1)  # a place to point at even for no row
+        u8 = lambda w: torch.empty((rows, w), dtype=torch.uint8, device=device)  # noqa: E731
+        self.hash = u8(32) if hash is None else hash
+        self.body = u8(512) if body is None else body
+        self.ids = u8(32) if ids is True else (None if ids is False else ids)
+        self.meta = torch.empty(rows, dtype=torch.int32, device=device) if meta is True else (
+            None if meta is False else meta)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device) if count is None else count
+        for name, t, dt, width in (("hash", self.hash, torch.uint8, 32), ("body", self.body, torch.uint8, 512),
+                                   ("ids", self.ids, torch.uint8, 32), ("meta", self.meta, torch.int32, None),
+                                   ("count", self.count, torch.int32, None)):
+            if t is None:
+                continue
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"nodes.{name} must be a contiguous CUDA tensor of {dt}")
+            need = 1 if name == "count" else self.max_nodes
+            if (t.dim() != 2 or t.shape[1] != width or t.shape[0] < need) if width else t.numel() < need:
+                raise ValueError(f"nodes.{name} has no room for max_nodes rows")
+
+    def struct(self):
+        return _nodes_struct(self.max_nodes, self.hash, self.body, self.ids, self.meta, self.count)
+
+    def rows(self):
+        """Waits for the device: the rows written, min(count, max_nodes)."""
+        return min(int(self.count.item()), self.max_nodes)
+
+
+class HostNodes:
+    """The same in host memory (numpy), filled by a host form: ``count`` is an
+    int once the call has returned, and the arrays hold ``rows()`` rows."""
+
+    def __init__(self, max_nodes, ids=True, meta=True):
+        self.max_nodes = int(max_nodes)
+        if not 0 <= self.max_nodes <= SHAMAP_MAX_NODES:
+            raise ValueError("max_nodes must be in 0 .. SHAMAP_MAX_NODES")
+        rows = max(self.max_nodes, 1)
+        self.hash = np.zeros((rows, 32), np.uint8)
+        self.body = np.zeros((rows, 512), np.uint8)
+        self.ids = np.zeros((rows, 32), np.uint8) if ids else None
+        self.meta = np.zeros(rows, np.uint32) if meta else None
+        self._count = np.zeros(1, np.uint32)
+
+    def struct(self):
+        return _nodes_struct(self.max_nodes, self.hash, self.body, self.ids, self.meta, self._count)
+
+    @property
+    def count(self):
+        return int(self._count[0])
+
+    def rows(self):
+        return min(self.count, self.max_nodes)
+
+
+def _node_counts(counts, words, device):
+    import torch
+    if counts is True:
+        return torch.empty(words, dtype=torch.int32, device=device)
+    if counts is False or counts is None:
+        return None
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (words,):
+        raise ValueError(f"counts must be int32[{words}]")
+    return counts
+
+
+def _device_nodes(nodes, max_nodes, ids, meta, device):
+    if nodes is not None:
+        if not isinstance(nodes, DeviceNodes):
+            raise ValueError("nodes must be a DeviceNodes")
+        return nodes
+    if max_nodes is None:
+        raise ValueError("give max_nodes (rows to make room for) or nodes (a DeviceNodes)")
+    return DeviceNodes(max_nodes, ids, meta, device)
+
+
+def shamap_nodes_device(keys, leaf_hashes=None, select_words=None, max_nodes=None, nodes=None, ids=True, meta=True,
+                        out_root=None, counts=True, stream=None):
+    """stl_shamap_nodes_device: ``shamap_root_device``, and every inner node of
+    the map stored once -> (root, counts, nodes): root (1, 32) uint8, counts
+    int32[4] (or None with ``counts=False``), nodes a ``DeviceNodes`` of
+    ``max_nodes`` rows (made here, or the one given).  A map of m keys has at
+    most 63 (m - 1) + 1 inner nodes; when nodes.count exceeds max_nodes the
+    arrays hold some max_nodes of them and root and counts are still right.
+    Asynchronous on ``stream``, no host wait."""
+    import torch
+    if keys.dim() != 2:
+        raise ValueError("keys must be (n, 32) bytes")
+    n = keys.shape[0]
+    _check_hashes(n, keys=keys, leaf_hashes=leaf_hashes)
+    if n > SHAMAP_MAX_ITEMS:
+        raise ValueError("more than SHAMAP_MAX_ITEMS rows")
+    if select_words is not None and (select_words.dtype != torch.int64 or select_words.numel() < (n + 63) // 64):
+        raise ValueError("select_words must be int64, one word per 64 rows")
+    if out_root is None:
+        out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
+    _check_hashes(1, out_root=out_root)
+    cnt = _node_counts(counts, 4, keys.device)
+    nodes = _device_nodes(nodes, max_nodes, ids, meta, keys.device)
+    for t in (keys, leaf_hashes, select_words, out_root, cnt):
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("device entry point needs contiguous CUDA tensors")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    out = nodes.struct()
+    N.check(N.load().stl_shamap_nodes_device(p(keys), p(leaf_hashes), p(select_words), n, p(out_root), p(cnt),
+                                             ctypes.byref(out), _stream_ptr(stream)), "stl_shamap_nodes_device")
+    return out_root, cnt, nodes
+
+
+def shamap_nodes(keys, leaf_hashes=None, select=None, max_nodes=0, ids=True, meta=True):
+    """stl_shamap_nodes: host memory, synchronous -> (32 root bytes, [4
+    counts], nodes): a ``HostNodes`` whose arrays hold min(count, max_nodes)
+    rows."""
+    keys = np.ascontiguousarray(keys)
+    if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+        raise ValueError("keys must be (n, 32) uint8")
+    n = keys.shape[0]
+    if leaf_hashes is not None:
+        leaf_hashes = np.ascontiguousarray(leaf_hashes)
+        if leaf_hashes.dtype != np.uint8 or leaf_hashes.shape != (n, 32):
+            raise ValueError("leaf_hashes must be (n, 32) uint8")
+    sel = None
+    if select is not None:
+        select = np.asarray(select)
+        if select.dtype != np.bool_ or select.shape != (n,):
+            raise ValueError("select must be bool[n]")
+        sel = np.packbits(select, bitorder="little") if n else np.zeros(1, np.uint8)
+    if n > SHAMAP_MAX_ITEMS:
+        raise ValueError("more than SHAMAP_MAX_ITEMS rows")
+    root = np.zeros(32, dtype=np.uint8)
+    cnt = np.zeros(4, dtype=np.uint32)
+    nodes = HostNodes(max_nodes, ids, meta)
+    out = nodes.struct()
+    N.check(N.load().stl_shamap_nodes(_buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n
+                                      else None, _buf(sel) if sel is not None else None, n, _buf(root), _buf(cnt),
+                                      ctypes.byref(out)), "stl_shamap_nodes")
+    return root.tobytes(), [int(x) for x in cnt], nodes
+
+
 # ---- registered signer sets (stl_keyset_*) ----
 
 class KeysetInfo(ctypes.Structure):
