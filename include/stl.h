@@ -521,6 +521,9 @@ int stl_debug_verify_k_device(const uint8_t *d_sig, const uint8_t *d_k, const ui
                                  bytes, so whatever a slot holds the accept bits are those of a fresh
                                  decoding.  A smaller value only masks the set index; entries left
                                  from another value are harmless. */
+#define STL_TUNE_SHAMAP_LOOKUP_BUCKETS 14 /* 0 / 1 (default 1): stl_shamap_tree_lookup* bisects the key's
+                                             bucket; 0 bisects the whole array (the A/B run of
+                                             tools/shamap_lookup_bench.py): the same outputs */
 int stl_debug_tuning(int key, int value);
 /* Caller-stream contexts libstl currently keeps on the current device. */
 int stl_debug_stream_contexts(void);
@@ -1042,6 +1045,83 @@ int stl_shamap_tree_apply_nodes_device(stl_shamap_tree *t, const uint8_t *d_key,
                                        const stl_shamap_nodes_out *out, void *stream);
 int stl_shamap_tree_apply_nodes(stl_shamap_tree *t, const uint8_t *key, const uint8_t *leaf_hash, const uint8_t *op,
                                 size_t n, uint8_t root[32], uint32_t counts[8], const stl_shamap_nodes_out *out);
+
+/* ---- resident SHAMap: hasItem, the item's hash and SHAMap::compare ----
+ * The node asks its maps all the time: applyTransactions drops a candidate the closed ledger already
+ * holds (hasTransaction, LedgerConsensus.cpp:1950), every disputed transaction is voted on per peer
+ * with set->hasItem(txID) (LedgerConsensus.cpp:853, 1319-1359), and createDisputes runs SHAMap::compare
+ * between our set and each peer's (LedgerConsensus.cpp:1263, SHAMapDelta.cpp:120).  The two calls
+ * below answer from a stl_shamap_tree where it lies.  Both only read: content, count and root of a
+ * tree are never changed by them, whatever they return.
+ *
+ * LOOKUP.  d_key: n * 32 bytes, 16-byte aligned.  d_found_words (required): ceil(n / 64) words in the
+ * accept bitmaps' layout, bit i set when key i is in the tree; the words are written whole and the
+ * last word's tail bits are zero (as stl_sigcache_lookup_device), so they combine with an accept
+ * bitmap into a select bitmap (candidates = accept & ~found).  d_leaf_hash (n * 32 bytes, 16-byte
+ * aligned, or NULL): the item's leaf hash, zeros for an absent key.  d_position (n words or NULL): the
+ * key's row in stl_shamap_tree_export_device's order, or 0xFFFFFFFF; valid until the next apply.
+ * Exactly those bytes are written; repeated keys are answered independently.  The item count is read
+ * on the device; one lane per key bisects the range of the key's bucket alone (its begin from a scan
+ * of the generation's 65,536 bucket counts, made per call).
+ * Before any device work: a NULL tree, a NULL d_found_words or d_key with n > 0, d_key or d_leaf_hash
+ * not 16-byte aligned, d_found_words not 8-byte or d_position not 4-byte aligned, n > 0xffffffc0, a
+ * handle that is not live or a tree of another device than the calling thread's is STL_EINVAL.
+ * n == 0 is STL_OK and writes nothing.
+ * MEMORY: 256 KiB of bucket begin positions and the scan's temporary storage in the stream context;
+ * nothing per key.
+ *
+ * COMPARE.  Let D be the differences of the two trees' contents: a key in exactly one tree, or in
+ * both with different leaf hashes.  The rows are D in ascending key order (memcmp order, the order
+ * of the reference's Delta map), truncated to the first max_rows; counts[0] is |D| whatever max_rows
+ * is.  SHAMap::compare returns false once it has counted maxCount differences: counts[0] >= max_rows
+ * is that condition -- but the rows here are the first ones in key order, not an unspecified part.
+ * No store goes past max_rows rows whatever the data.  a == b is allowed: no difference.
+ * BUCKET RULE (the reference's own assumption): a bucket -- the keys that share their first 4
+ * nibbles -- whose (count, hash) is equal in both trees is taken as equal and not examined, as
+ * SHAMap::compare does not descend into a branch with equal hashes.  That is exact when a leaf hash
+ * commits to its key, which every SHAMap leaf kind does ("MLN\0" || data || index, "SND\0" || ... ||
+ * id, and leaf = key for tnTRANSACTION_NM); leaf hashes that did not could hide a difference, here as
+ * there.  counts[4] and counts[5] say what was examined: the cost follows what
+ * differs, not what the trees hold.
+ * Before any device work: a NULL tree, out or counts, a struct_size other than
+ * sizeof(stl_shamap_diff_out), max_rows > STL_SHAMAP_MAX_NODES, max_rows > 0 with a NULL key or kind,
+ * in the device form key, leaf_a or leaf_b not 16-byte aligned or counts not 4-byte aligned, trees of
+ * different devices or of another device than the calling thread's, or a handle that is not live is
+ * STL_EINVAL.
+ * FAILURE: counts is written by the call's last kernel alone, so a call that failed has not written
+ * it; the row arrays may be partly written.
+ * MEMORY: 16 B per slot in the stream context -- a slot per item the host's bounds of the two counts
+ * admit (see CAPACITY above) -- plus 1 MiB of per-bucket words and the scans' temporary storage.
+ * The host form stages min(max_rows, slots) * 97 bytes on the device, waits once for counts[0] and
+ * copies back min(counts[0], max_rows) rows; a host array may have any alignment.
+ *
+ * Both device forms are asynchronous on `stream` and never wait on the host; the host forms are
+ * synchronous: upload, the device form, copy back.
+ * Concurrency: lookups and compares only read trees and may run concurrently with each other, on
+ * any streams.  With respect to an apply on the same tree the caller orders them, as it orders
+ * applies: they read the generation that is live when they are called. */
+int stl_shamap_tree_lookup_device(stl_shamap_tree *t, const uint8_t *d_key, size_t n, uint64_t *d_found_words,
+                                  uint8_t *d_leaf_hash, uint32_t *d_position, void *stream);
+/* found_bitmap: ceil(n / 8) bytes, bit i of byte i / 8. */
+int stl_shamap_tree_lookup(stl_shamap_tree *t, const uint8_t *key, size_t n, uint8_t *found_bitmap,
+                           uint8_t *leaf_hash, uint32_t *position);
+#define STL_SHAMAP_DIFF_A_ONLY 1u  /* DeltaItem (item, null) */
+#define STL_SHAMAP_DIFF_B_ONLY 2u  /* DeltaItem (null, item) */
+#define STL_SHAMAP_DIFF_CHANGED 3u /* in both, leaf hashes differ */
+typedef struct stl_shamap_diff_out {
+  uint32_t struct_size; /* sizeof(stl_shamap_diff_out) */
+  uint32_t max_rows;    /* rows the arrays have room for (the reference's maxCount) */
+  uint8_t *key;         /* max_rows * 32, required unless max_rows == 0 */
+  uint8_t *kind;        /* max_rows bytes, required unless max_rows == 0: STL_SHAMAP_DIFF_* */
+  uint8_t *leaf_a;      /* max_rows * 32 or NULL: the item's leaf hash in a, zeros for B_ONLY */
+  uint8_t *leaf_b;      /* max_rows * 32 or NULL: ... in b, zeros for A_ONLY */
+  uint32_t *counts;     /* 8 words, required: [0] differences (may exceed max_rows), [1] A_ONLY,
+                           [2] B_ONLY, [3] CHANGED, [4] buckets examined, [5] items examined
+                           (those buckets' items of a plus of b), [6] items of a, [7] items of b */
+} stl_shamap_diff_out;
+int stl_shamap_tree_compare_device(stl_shamap_tree *a, stl_shamap_tree *b, const stl_shamap_diff_out *out,
+                                   void *stream);
+int stl_shamap_tree_compare(stl_shamap_tree *a, stl_shamap_tree *b, const stl_shamap_diff_out *out);
 
 #ifdef __cplusplus
 }

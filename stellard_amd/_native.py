@@ -55,6 +55,7 @@ STL_TUNE_WIDE_MIN_ROWS = 10
 STL_TUNE_R_AHEAD = 11
 STL_TUNE_FIRST_CHUNK = 12
 STL_TUNE_KEY_CACHE = 13
+STL_TUNE_SHAMAP_LOOKUP_BUCKETS = 14
 
 # per-transaction status of the serialized-transaction entry points
 STL_TX_OK = 0
@@ -91,6 +92,11 @@ STL_SHAMAP_MAX_ITEMS = 16777216
 # SHAMap inner nodes (stl_shamap_nodes*, stl_shamap_tree_apply_nodes*)
 STL_SHAMAP_MAX_NODES = 0xFFFFFFC0
 STL_SHAMAP_NODE_BODY_BYTES = 512
+
+# resident SHAMap compare (stl_shamap_tree_compare*)
+STL_SHAMAP_DIFF_A_ONLY = 1
+STL_SHAMAP_DIFF_B_ONLY = 2
+STL_SHAMAP_DIFF_CHANGED = 3
 
 # arithmetic self-test (stl_debug_selftest_*; row formats in csrc/stl_selftest.h)
 STL_SELFTEST_OPS = 47
@@ -211,6 +217,10 @@ SYMBOLS = [
     ("stl_shamap_tree_apply_nodes_device", ctypes.c_int,
      [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P, _P]),
     ("stl_shamap_tree_apply_nodes", ctypes.c_int, [_P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_tree_lookup_device", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _P, _U8P, _P, _P]),
+    ("stl_shamap_tree_lookup", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _U8P, _U8P, _P]),
+    ("stl_shamap_tree_compare_device", ctypes.c_int, [_P, _P, _P, _P]),
+    ("stl_shamap_tree_compare", ctypes.c_int, [_P, _P, _P]),
 ]
 
 
@@ -219,6 +229,13 @@ class ShamapNodesOut(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("max_nodes", ctypes.c_uint32), ("hash", ctypes.c_void_p),
                 ("body", ctypes.c_void_p), ("id", ctypes.c_void_p), ("meta", ctypes.c_void_p),
                 ("count", ctypes.c_void_p)]
+
+
+class ShamapDiffOut(ctypes.Structure):
+    """stl_shamap_diff_out (include/stl.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_rows", ctypes.c_uint32), ("key", ctypes.c_void_p),
+                ("kind", ctypes.c_void_p), ("leaf_a", ctypes.c_void_p), ("leaf_b", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p)]
 
 
 VERDICT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)

@@ -19,6 +19,9 @@
                                  position and top rules and its staged apply
   tests/native/libhostemu_shamap_nodes.so  the stored inner nodes' masking,
                                  leaf and top rules and both staged calls
+  tests/native/libhostemu_shamap_lookup.so  the resident SHAMap's in-bucket
+                                 search, bucket-differs and rank rules and the
+                                 staged lookup and compare
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -36,7 +39,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
-                "stl_shamap.hip", "stl_shamap_tree.hip", "stl_selftest.hip",
+                "stl_shamap.hip", "stl_shamap_tree.hip", "stl_shamap_lookup.hip", "stl_selftest.hip",
                 "stl_api.cpp", "stl_api_keyset.cpp", "stl_api_authority.cpp", "stl_api_sigcache.cpp",
                 "stl_api_shamap.cpp", "stl_api_shamap_tree.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
@@ -47,6 +50,7 @@ PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe2551
                                "stl_sigcache_core.h", "stl_sigcache.h",
                                "stl_shamap_core.h", "stl_shamap.h",
                                "stl_shamap_tree_core.h", "stl_shamap_tree.h",
+                               "stl_shamap_lookup_core.h", "stl_shamap_lookup.h",
                                "stl_group.h", "stl_selftest.h", "stl_host.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
@@ -82,7 +86,7 @@ def _run(cmd, cwd=ROOT):
 HOST_ONLY = ["stl_host.h"]
 HOST_DEPS = HOST_ONLY + ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
              "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", "stl_shamap.h",
-             "stl_shamap_tree.h", "stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h", os.path.join("..", "..", "include", "stl.h")]
+             "stl_shamap_tree.h", "stl_shamap_tree_core.h", "stl_shamap_lookup.h", "stl_shamap_core.h", "stl_sha512.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -151,6 +155,8 @@ SMALL_HARNESSES = {
                                                 "stl_fe25519.h")),
     "shamap_nodes": ("hostemu_shamap_nodes.cpp", ("stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
                                                   "stl_fe25519.h")),
+    "shamap_lookup": ("hostemu_shamap_lookup.cpp", ("stl_shamap_lookup_core.h", "stl_shamap_tree_core.h",
+                                                    "stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -208,6 +214,10 @@ def build_hostemu_shamap_nodes(force=False):
     return _build_small("shamap_nodes", force)
 
 
+def build_hostemu_shamap_lookup(force=False):
+    return _build_small("shamap_lookup", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -232,7 +242,7 @@ def main(argv=None):
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
                 ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force),
-                ex.submit(build_hostemu_shamap_nodes, force)]
+                ex.submit(build_hostemu_shamap_nodes, force), ex.submit(build_hostemu_shamap_lookup, force)]
         for j in jobs:
             j.result()
     build_oracle()

@@ -412,6 +412,10 @@ int ensure_init() {
 }
 
 std::atomic<int>& max_caller_streams() { return g_max_caller_streams; }
+std::atomic<int>& tune_lookup_buckets() {
+  static std::atomic<int> on{1};
+  return on;
+}
 
 // The context of stream s on device d (created on first use).  Creating a
 // caller stream's context beyond the cap evicts the least recently used
@@ -1281,6 +1285,7 @@ int stl_debug_tuning(int key, int value) {
       case STL_TUNE_RCCL_TIMEOUT_MS: return g_rccl_timeout_ms.load();
       case STL_TUNE_LONG_HASH: return g_tune_long_hash.load();
       case STL_TUNE_KEY_CACHE: return key_cache_in_use();
+      case STL_TUNE_SHAMAP_LOOKUP_BUCKETS: return tune_lookup_buckets().load();
       default: return STL_EINVAL;
     }
   }
@@ -1330,6 +1335,9 @@ int stl_debug_tuning(int key, int value) {
       g_tune_key_cache.store(value);
       return prev;
     }
+    case STL_TUNE_SHAMAP_LOOKUP_BUCKETS:
+      if (value != 0 && value != 1) return STL_EINVAL;
+      return tune_lookup_buckets().exchange(value);
     default:
       return STL_EINVAL;
   }

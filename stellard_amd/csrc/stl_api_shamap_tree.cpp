@@ -1,9 +1,11 @@
 // stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
-// ledger's changes, and the inner nodes an apply makes new): the
-// stl_shamap_tree_* entry points of include/stl.h;
-// kernels: stl_shamap_tree.hip, and the sort and level kernels of stl_shamap.hip.
+// ledger's changes, the inner nodes an apply makes new, lookup by key and the
+// difference of two trees): the stl_shamap_tree_* entry points of include/stl.h;
+// kernels: stl_shamap_tree.hip, stl_shamap_lookup.hip, and the sort and level
+// kernels of stl_shamap.hip.
 #include "stl_host.h"
 #include "stl_shamap.h"
+#include "stl_shamap_lookup.h"
 #include "stl_shamap_tree.h"
 #include "stl_shamap_tree_core.h"
 
@@ -111,6 +113,63 @@ int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint
 void tree_commit(stl_shamap_tree* t, uint32_t bound_after) {
   t->live ^= 1;
   t->bound = bound_after;
+}
+
+// ---- the read-only calls: nothing below changes *t ----
+int check_lookup_args(const stl_shamap_tree* t, const void* key, size_t n, const void* found, const void* leaf,
+                      const void* position, bool device_form) {
+  if (!t || n > STL_SHAMAP_MAX_NODES || (n && (!key || !found))) return STL_EINVAL;
+  if (!device_form) return STL_OK;  // host arrays: any alignment serves
+  if (((uintptr_t)key & 15u) != 0 || ((uintptr_t)leaf & 15u) != 0) return STL_EINVAL;
+  if (((uintptr_t)found & 7u) != 0 || ((uintptr_t)position & 3u) != 0) return STL_EINVAL;
+  return STL_OK;
+}
+
+// The lookup of n >= 1 keys in t's live generation on stream s (g_trees.mu held,
+// t live on d): enqueued, never waited for.
+int lookup_enqueue(Device& d, const stl_shamap_tree* t, const uint8_t* d_key, size_t n, uint64_t* d_words,
+                   uint8_t* d_leaf, uint32_t* d_position, hipStream_t s) {
+  size_t temp = 0;
+  STL_TRY(stl::shamap_temp_bytes(stl::kTreeBuckets, &temp));
+  const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
+  std::lock_guard<std::mutex> lk(c->mu);
+  STL_RC(c->shamap.ensure(stl::shamap_lookup_workspace_bytes(temp)));
+  STL_TRY(stl::launch_shamap_tree_lookup(t->gen(t->live), t->capacity, d_key, (uint32_t)n, d_words, d_leaf, d_position,
+                                         tune_lookup_buckets().load() != 0, c->shamap.p, temp, fault_now, s));
+  return STL_OK;
+}
+
+int check_compare_args(const stl_shamap_tree* a, const stl_shamap_tree* b, const stl_shamap_diff_out* out,
+                       bool device_form) {
+  if (!a || !b || !out || out->struct_size != sizeof(stl_shamap_diff_out) || !out->counts) return STL_EINVAL;
+  if (out->max_rows > STL_SHAMAP_MAX_NODES || (out->max_rows && (!out->key || !out->kind))) return STL_EINVAL;
+  if (!device_form) return STL_OK;
+  if ((((uintptr_t)out->key | (uintptr_t)out->leaf_a | (uintptr_t)out->leaf_b) & 15u) != 0) return STL_EINVAL;
+  if (((uintptr_t)out->counts & 3u) != 0) return STL_EINVAL;
+  return STL_OK;
+}
+
+// Both handles live and on the calling thread's device (g_trees.mu held).
+int trees_for_call(const stl_shamap_tree* a, const stl_shamap_tree* b, Device** d) {
+  if (!g_trees.live(a) || !g_trees.live(b)) return STL_EINVAL;
+  STL_RC(g_trees.for_call(a, d));
+  return b->ordinal == a->ordinal ? STL_OK : STL_EINVAL;
+}
+
+// The slots a compare is sized for: no more items can differ than both trees hold.
+uint32_t compare_slots(const stl_shamap_tree* a, const stl_shamap_tree* b) { return a->bound + b->bound; }
+
+int compare_enqueue(Device& d, const stl_shamap_tree* a, const stl_shamap_tree* b, const stl::ShamapDiff& out,
+                    hipStream_t s) {
+  const uint32_t slots = compare_slots(a, b);
+  size_t temp = 0;
+  STL_TRY(stl::shamap_temp_bytes(slots > stl::kTreeBuckets ? slots : stl::kTreeBuckets, &temp));
+  const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
+  std::lock_guard<std::mutex> lk(c->mu);
+  STL_RC(c->shamap.ensure(stl::shamap_compare_workspace_bytes(slots, temp)));
+  STL_TRY(stl::launch_shamap_tree_compare(a->gen(a->live), a->capacity, b->gen(b->live), b->capacity, slots, out,
+                                          c->shamap.p, temp, fault_now, s));
+  return STL_OK;
 }
 }  // namespace
 
@@ -301,6 +360,86 @@ int stl_shamap_tree_export_device(stl_shamap_tree* t, uint8_t* d_key, uint8_t* d
   STL_TRY(stl::launch_shamap_tree_export(t->gen(t->live), t->bound, d_key, d_leaf_hash, (uint32_t)rows, d_items,
                                          static_cast<hipStream_t>(stream)));
   return STL_OK;
+}
+
+int stl_shamap_tree_lookup_device(stl_shamap_tree* t, const uint8_t* d_key, size_t n, uint64_t* d_found_words,
+                                  uint8_t* d_leaf_hash, uint32_t* d_position, void* stream) {
+  STL_RC(check_lookup_args(t, d_key, n, d_found_words, d_leaf_hash, d_position, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  if (n == 0) return STL_OK;
+  return lookup_enqueue(*d, t, d_key, n, d_found_words, d_leaf_hash, d_position, static_cast<hipStream_t>(stream));
+}
+
+int stl_shamap_tree_lookup(stl_shamap_tree* t, const uint8_t* key, size_t n, uint8_t* found_bitmap,
+                           uint8_t* leaf_hash, uint32_t* position) {
+  STL_RC(check_lookup_args(t, key, n, found_bitmap, leaf_hash, position, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(g_trees.for_call(t, &dp));
+  if (n == 0) return STL_OK;
+  HostCall call("stl_shamap_tree_lookup", n, *dp);
+  return call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(call.upload(d.pk, key, n * 32));
+    STL_RC(d.bitmap.ensure((n + 63) / 64 * 8));
+    if (leaf_hash) STL_RC(d.msg.ensure(n * 32));
+    if (position) STL_RC(d.off.ensure(n * 4));
+    STL_RC(lookup_enqueue(d, t, static_cast<const uint8_t*>(d.pk.p), n, static_cast<uint64_t*>(d.bitmap.p),
+                          leaf_hash ? static_cast<uint8_t*>(d.msg.p) : nullptr,
+                          position ? static_cast<uint32_t*>(d.off.p) : nullptr, d.stream));
+    call.download(found_bitmap, d.bitmap, (n + 7) / 8);
+    call.download(leaf_hash, d.msg, n * 32);
+    call.download(position, d.off, n * 4);
+    return STL_OK;
+  });
+}
+
+int stl_shamap_tree_compare_device(stl_shamap_tree* a, stl_shamap_tree* b, const stl_shamap_diff_out* out,
+                                   void* stream) {
+  STL_RC(check_compare_args(a, b, out, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(trees_for_call(a, b, &d));
+  const stl::ShamapDiff diff{out->key, out->kind, out->leaf_a, out->leaf_b, out->max_rows, out->counts};
+  return compare_enqueue(*d, a, b, diff, static_cast<hipStream_t>(stream));
+}
+
+int stl_shamap_tree_compare(stl_shamap_tree* a, stl_shamap_tree* b, const stl_shamap_diff_out* out) {
+  STL_RC(check_compare_args(a, b, out, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(trees_for_call(a, b, &dp));
+  HostCall call("stl_shamap_tree_compare", out->max_rows, *dp);
+  return call.run([&]() -> int {
+    Device& d = call.d;
+    // no more rows can come back than both trees hold
+    const uint32_t slots = compare_slots(a, b);
+    const uint32_t room = out->max_rows < slots ? out->max_rows : slots;
+    const size_t stage = room ? room : 1;  // a place to point at even for no row
+    STL_RC(d.pk.ensure(32 * stage));
+    STL_RC(d.sig.ensure(stage));
+    if (out->leaf_a) STL_RC(d.msg.ensure(32 * stage));
+    if (out->leaf_b) STL_RC(d.wide.ensure(32 * stage));
+    STL_RC(d.status.ensure(32));
+    const stl::ShamapDiff diff{static_cast<uint8_t*>(d.pk.p), static_cast<uint8_t*>(d.sig.p),
+                               out->leaf_a ? static_cast<uint8_t*>(d.msg.p) : nullptr,
+                               out->leaf_b ? static_cast<uint8_t*>(d.wide.p) : nullptr, room,
+                               static_cast<uint32_t*>(d.status.p)};
+    STL_RC(compare_enqueue(d, a, b, diff, d.stream));
+    uint32_t differences = 0;
+    STL_TRY(hipMemcpyAsync(&differences, d.status.p, 4, hipMemcpyDeviceToHost, d.stream));
+    STL_TRY(hipStreamSynchronize(d.stream));  // the one wait of its own: how many rows to bring back
+    const size_t rows = differences < room ? differences : room;
+    call.download(out->counts, d.status, 32);
+    if (!rows) return STL_OK;
+    call.download(out->key, d.pk, 32 * rows);
+    call.download(out->kind, d.sig, rows);
+    call.download(out->leaf_a, d.msg, 32 * rows);
+    call.download(out->leaf_b, d.wide, 32 * rows);
+    return STL_OK;
+  });
 }
 
 }  // extern "C"

@@ -364,6 +364,8 @@ int check_flags(uint32_t flags);
 inline int check_keyset_flags(uint32_t flags) {
   return (flags & ~(STL_POLICY_MASK | STL_REQUIRE_S_LT_L | STL_DEBUG_RAW_PREDICATE)) ? STL_EINVAL : STL_OK;
 }
+// STL_TUNE_SHAMAP_LOOKUP_BUCKETS: 1 (default) a tree lookup bisects the key's bucket, 0 the whole array
+std::atomic<int>& tune_lookup_buckets();
 uint64_t now_ns();
 
 // Counts one host entry-point call: signatures, wall time, errors; with

@@ -1015,6 +1015,158 @@ class ShamapTree(_DeviceObject):
             "stl_shamap_tree_apply_nodes")
         return root.tobytes(), [int(x) for x in cnt], nodes
 
+    def lookup_device(self, keys, out_words=None, leaf_hashes=False, positions=False, stream=None):
+        """stl_shamap_tree_lookup_device: keys (n, 32) uint8 in HBM -> found
+        words int64[ceil(n/64)] (the accept bitmaps' layout), or (words,
+        leaf_hashes, positions) when either is asked for: ``leaf_hashes`` /
+        ``positions`` True (made here), a tensor to write ((n, 32) uint8: zeros
+        for an absent key; int32[n]: the row in ``export_device``'s order or
+        -1), or False (not written, None).  Asynchronous on ``stream``."""
+        import torch
+        if keys.dim() != 2:
+            raise ValueError("keys must be (n, 32) bytes")
+        n = keys.shape[0]
+        _check_hashes(n, keys=keys)
+        if out_words is None:
+            out_words = torch.empty(((n + 63) // 64,), dtype=torch.int64, device=keys.device)
+        if out_words.dtype != torch.int64 or out_words.numel() < (n + 63) // 64:
+            raise ValueError("out_words must be int64, one word per 64 rows")
+        leaf = torch.empty((n, 32), dtype=torch.uint8, device=keys.device) if leaf_hashes is True else (
+            None if leaf_hashes is False or leaf_hashes is None else leaf_hashes)
+        _check_hashes(n, leaf_hashes=leaf)
+        pos = torch.empty(n, dtype=torch.int32, device=keys.device) if positions is True else (
+            None if positions is False or positions is None else positions)
+        if pos is not None and (pos.dtype != torch.int32 or tuple(pos.shape) != (n,)):
+            raise ValueError("positions must be int32[n]")
+        for t in (keys, out_words, leaf, pos):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        N.check(N.load().stl_shamap_tree_lookup_device(self._h, p(keys), n, p(out_words), p(leaf), p(pos),
+                                                       _stream_ptr(stream)), "stl_shamap_tree_lookup_device")
+        return out_words if leaf is None and pos is None else (out_words, leaf, pos)
+
+    def lookup(self, keys, leaf_hashes=False, positions=False):
+        """stl_shamap_tree_lookup: host memory, synchronous.  keys (n, 32)
+        uint8 -> found bool[n], or (found, leaf hashes (n, 32) or None,
+        positions uint32[n] or None) when either is asked for."""
+        keys = np.ascontiguousarray(keys)
+        if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+            raise ValueError("keys must be (n, 32) uint8")
+        n = keys.shape[0]
+        bitmap = np.zeros((n + 7) // 8 or 1, dtype=np.uint8)
+        leaf = np.zeros((max(n, 1), 32), np.uint8) if leaf_hashes else None
+        pos = np.zeros(max(n, 1), np.uint32) if positions else None
+        N.check(N.load().stl_shamap_tree_lookup(self._h, _buf(keys) if n else None, n, _buf(bitmap),
+                                                _buf(leaf) if leaf is not None else None,
+                                                _buf(pos) if pos is not None else None), "stl_shamap_tree_lookup")
+        found = unpack_bitmap(bitmap, n)
+        if not leaf_hashes and not positions:
+            return found
+        return found, leaf[:n] if leaf is not None else None, pos[:n] if pos is not None else None
+
+    def compare_device(self, other, max_rows=None, diff=None, leaf_a=True, leaf_b=True, stream=None):
+        """stl_shamap_tree_compare_device: the differences of this tree (a) and
+        ``other`` (b) -> a DeviceDiff: rows in key order, the first ``max_rows``
+        of them, and int32[8] counts.  Asynchronous on ``stream``."""
+        if not isinstance(other, ShamapTree):
+            raise ValueError("other must be a ShamapTree")
+        if diff is None:
+            if max_rows is None:
+                raise ValueError("give max_rows (rows to make room for) or diff (a DeviceDiff)")
+            diff = DeviceDiff(max_rows, leaf_a, leaf_b)
+        elif not isinstance(diff, DeviceDiff):
+            raise ValueError("diff must be a DeviceDiff")
+        out = diff.struct()
+        N.check(N.load().stl_shamap_tree_compare_device(self._h, other._h, ctypes.byref(out), _stream_ptr(stream)),
+                "stl_shamap_tree_compare_device")
+        return diff
+
+    def compare(self, other, max_rows=0, leaf_a=True, leaf_b=True):
+        """stl_shamap_tree_compare: host memory, synchronous -> a HostDiff
+        whose arrays hold ``rows()`` rows."""
+        if not isinstance(other, ShamapTree):
+            raise ValueError("other must be a ShamapTree")
+        diff = HostDiff(max_rows, leaf_a, leaf_b)
+        out = diff.struct()
+        N.check(N.load().stl_shamap_tree_compare(self._h, other._h, ctypes.byref(out)), "stl_shamap_tree_compare")
+        return diff
+
+
+# ---- the difference of two resident trees (stl_shamap_tree_compare*) ----
+
+SHAMAP_DIFF_A_ONLY = N.STL_SHAMAP_DIFF_A_ONLY
+SHAMAP_DIFF_B_ONLY = N.STL_SHAMAP_DIFF_B_ONLY
+SHAMAP_DIFF_CHANGED = N.STL_SHAMAP_DIFF_CHANGED
+
+
+def _diff_struct(max_rows, key, kind, leaf_a, leaf_b, counts):
+    p = lambda a: a if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)  # noqa: E731
+    return N.ShamapDiffOut(ctypes.sizeof(N.ShamapDiffOut), max_rows, p(key), p(kind), p(leaf_a), p(leaf_b), p(counts))
+
+
+class DeviceDiff:
+    """The rows a device compare writes, as CUDA tensors of ``max_rows`` rows:
+    key (max_rows, 32) uint8, kind uint8[max_rows] (SHAMAP_DIFF_*), leaf_a /
+    leaf_b (max_rows, 32) uint8 or None, counts int32[8] -- [0] the
+    differences, which may exceed max_rows.  Tensors given are written in place."""
+
+    def __init__(self, max_rows, leaf_a=True, leaf_b=True, device="cuda", key=None, kind=None, counts=None):
+        import torch
+        self.max_rows = int(max_rows)
+        if not 0 <= self.max_rows <= SHAMAP_MAX_NODES:
+            raise ValueError("max_rows must be in 0 .. SHAMAP_MAX_NODES")
+        rows = max(self.max_rows, 1)  # a place to point at even for no row
+        u8 = lambda: torch.empty((rows, 32), dtype=torch.uint8, device=device)  # noqa: E731
+        self.key = u8() if key is None else key
+        self.kind = torch.empty(rows, dtype=torch.uint8, device=device) if kind is None else kind
+        self.leaf_a = u8() if leaf_a is True else (None if leaf_a is False or leaf_a is None else leaf_a)
+        self.leaf_b = u8() if leaf_b is True else (None if leaf_b is False or leaf_b is None else leaf_b)
+        self.counts = torch.zeros(8, dtype=torch.int32, device=device) if counts is None else counts
+        for name, t, dt, width in (("key", self.key, torch.uint8, 32), ("kind", self.kind, torch.uint8, None),
+                                   ("leaf_a", self.leaf_a, torch.uint8, 32), ("leaf_b", self.leaf_b, torch.uint8, 32),
+                                   ("counts", self.counts, torch.int32, None)):
+            if t is None:
+                continue
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"diff.{name} must be a contiguous CUDA tensor of {dt}")
+            need = 8 if name == "counts" else self.max_rows
+            if (t.dim() != 2 or t.shape[1] != width or t.shape[0] < need) if width else t.numel() < need:
+                raise ValueError(f"diff.{name} has no room for {'8 counts' if name == 'counts' else 'max_rows rows'}")
+
+    def struct(self):
+        return _diff_struct(self.max_rows, self.key, self.kind, self.leaf_a, self.leaf_b, self.counts)
+
+    def rows(self):
+        """Waits for the device: the rows written, min(counts[0], max_rows)."""
+        return min(int(self.counts[0].item()), self.max_rows)
+
+
+class HostDiff:
+    """The same in host memory (numpy), filled by the host form: ``counts`` is
+    a list of 8 ints once the call has returned."""
+
+    def __init__(self, max_rows, leaf_a=True, leaf_b=True):
+        self.max_rows = int(max_rows)
+        if not 0 <= self.max_rows <= SHAMAP_MAX_NODES:
+            raise ValueError("max_rows must be in 0 .. SHAMAP_MAX_NODES")
+        rows = max(self.max_rows, 1)
+        self.key = np.zeros((rows, 32), np.uint8)
+        self.kind = np.zeros(rows, np.uint8)
+        self.leaf_a = np.zeros((rows, 32), np.uint8) if leaf_a else None
+        self.leaf_b = np.zeros((rows, 32), np.uint8) if leaf_b else None
+        self._counts = np.zeros(8, np.uint32)
+
+    def struct(self):
+        return _diff_struct(self.max_rows, self.key, self.kind, self.leaf_a, self.leaf_b, self._counts)
+
+    @property
+    def counts(self):
+        return [int(x) for x in self._counts]
+
+    def rows(self):
+        return min(int(self._counts[0]), self.max_rows)
+
 
 # ---- SHAMap inner nodes (stl_shamap_nodes*, stl_shamap_tree_apply_nodes*) ----
 
