@@ -1123,6 +1123,63 @@ int stl_shamap_tree_compare_device(stl_shamap_tree *a, stl_shamap_tree *b, const
                                    void *stream);
 int stl_shamap_tree_compare(stl_shamap_tree *a, stl_shamap_tree *b, const stl_shamap_diff_out *out);
 
+/* ---- resident SHAMap: SHAMap::snapShot as a fork into another handle, and a one-step revert ----
+ * The reference starts every new ledger from prevLedger.mAccountStateMap->snapShot(true)
+ * (Ledger.cpp:153) and every changed position from mAcquired[...]->snapShot(true)
+ * (LedgerConsensus.cpp:1565-1591): the map it started from stays as it was.  A fork is that step for
+ * resident trees: the apply reads one generation and writes another, and here the other generation
+ * belongs to a different tree.
+ * FORK: after a successful call dst holds src's content with the batch applied.  The batch follows
+ * stl_shamap_tree_apply_device's rules (set or delete per row, the last of equal keys counts,
+ * d_leaf_hash NULL: the leaf hash is the key); d_root and the eight d_counts are what that apply on
+ * src would have written; dst's root, bucket values and count are those of its new content
+ * (stl_shamap_root_device over dst's export gives the same root).  Whatever dst held before is
+ * replaced -- and is what a revert of dst brings back.
+ * src IS ONLY READ: its content, count, root, bucket values and revert state are unchanged; neither
+ * of its generations and none of its work areas is written (every work area is dst's or the stream
+ * context's), so forks of one src into different dsts on different streams may run at the same
+ * time.  As with lookup and compare, the caller orders a fork against applies to src.
+ * n == 0 IS THE PLAIN SNAPSHOT: dst becomes a copy of src.  Nothing is hashed or sorted: the rows
+ * (by the count on the device, not the capacity), the 65,536 bucket values and the meta words are
+ * copied by one kernel; the outputs are those of an apply of no rows to src.
+ * CAPACITIES MAY DIFFER: dst only has to hold the result.  While src's host bound + n <= dst's
+ * capacity the call enqueues and returns without a wait; otherwise it takes the apply's one-wait
+ * path (the exact count of src, what the batch inserts and deletes), and if the result would not
+ * fit dst it is STL_ENOMEM and both trees stay as they were.  Every read of src's rows is clamped
+ * by min(count on the device, src's capacity), every store guarded by dst's capacity.
+ * Before any device work: the apply's checks (on dst: n > dst's capacity is STL_EINVAL); src NULL
+ * or src == dst, a handle that is not live, two trees of different devices or not of the calling
+ * thread's device are STL_EINVAL.
+ * FAILURE: a negative return leaves dst's content, count and root as they were (the live generation
+ * is never written; the device forms commit after the last enqueue, the host forms once the results
+ * are back) and src is never changed.  The caller's outputs are written by the last launch alone.
+ * The _nodes forms are stl_shamap_tree_apply_nodes[_device] with src as the old tree: the rows are
+ * the nodes of the dirty buckets and of the prefixes above them in dst's new tree, numbered, counted
+ * and cut off at max_nodes in the same way; n == 0 stores no node and writes a count of zero.  The
+ * normal close is one such call: fork the closed ledger's state into the next ledger's tree and hand
+ * the new nodes to the node store.
+ *
+ * REVERT: stl_shamap_tree_revert(t) makes t what it was before the last successful apply or fork
+ * into it -- content, count, root and bucket values -- by turning the host back to the previous
+ * generation and to the host bound that went with it: no device work, no wait; the caller orders it
+ * like an apply.  One step only: STL_EINVAL on a tree that has taken no apply, directly after a
+ * revert, and after any apply or fork into t that returned a negative code past its argument checks
+ * (that call may have half written the very generation a revert would turn to) until the next
+ * successful one.  An apply of no rows changes nothing, this included.  Positions from earlier
+ * lookups are invalid after a revert, as after an apply. */
+int stl_shamap_tree_fork_device(stl_shamap_tree *src, stl_shamap_tree *dst, const uint8_t *d_key,
+                                const uint8_t *d_leaf_hash, const uint8_t *d_op, size_t n, uint8_t *d_root,
+                                uint32_t *d_counts, void *stream);
+int stl_shamap_tree_fork(stl_shamap_tree *src, stl_shamap_tree *dst, const uint8_t *key, const uint8_t *leaf_hash,
+                         const uint8_t *op, size_t n, uint8_t root[32], uint32_t counts[8]);
+int stl_shamap_tree_fork_nodes_device(stl_shamap_tree *src, stl_shamap_tree *dst, const uint8_t *d_key,
+                                      const uint8_t *d_leaf_hash, const uint8_t *d_op, size_t n, uint8_t *d_root,
+                                      uint32_t *d_counts, const stl_shamap_nodes_out *out, void *stream);
+int stl_shamap_tree_fork_nodes(stl_shamap_tree *src, stl_shamap_tree *dst, const uint8_t *key,
+                               const uint8_t *leaf_hash, const uint8_t *op, size_t n, uint8_t root[32],
+                               uint32_t counts[8], const stl_shamap_nodes_out *out);
+int stl_shamap_tree_revert(stl_shamap_tree *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,12 @@ SYMBOLS = [
     ("stl_shamap_tree_lookup", ctypes.c_int, [_P, _U8P, ctypes.c_size_t, _U8P, _U8P, _P]),
     ("stl_shamap_tree_compare_device", ctypes.c_int, [_P, _P, _P, _P]),
     ("stl_shamap_tree_compare", ctypes.c_int, [_P, _P, _P]),
+    ("stl_shamap_tree_fork_device", ctypes.c_int, [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_tree_fork", ctypes.c_int, [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P]),
+    ("stl_shamap_tree_fork_nodes_device", ctypes.c_int,
+     [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P, _P]),
+    ("stl_shamap_tree_fork_nodes", ctypes.c_int, [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
+    ("stl_shamap_tree_revert", ctypes.c_int, [_P]),
 ]
 
 

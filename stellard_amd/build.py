@@ -22,6 +22,9 @@
   tests/native/libhostemu_shamap_lookup.so  the resident SHAMap's in-bucket
                                  search, bucket-differs and rank rules and the
                                  staged lookup and compare
+  tests/native/libhostemu_shamap_fork.so  the resident SHAMap's read clamp,
+                                 the staged fork between trees of two
+                                 capacities, the snapshot and the revert
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -157,6 +160,8 @@ SMALL_HARNESSES = {
                                                   "stl_fe25519.h")),
     "shamap_lookup": ("hostemu_shamap_lookup.cpp", ("stl_shamap_lookup_core.h", "stl_shamap_tree_core.h",
                                                     "stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
+    "shamap_fork": ("hostemu_shamap_fork.cpp", ("stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
+                                                "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -218,6 +223,10 @@ def build_hostemu_shamap_lookup(force=False):
     return _build_small("shamap_lookup", force)
 
 
+def build_hostemu_shamap_fork(force=False):
+    return _build_small("shamap_fork", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -242,7 +251,8 @@ def main(argv=None):
                 ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
                 ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force),
-                ex.submit(build_hostemu_shamap_nodes, force), ex.submit(build_hostemu_shamap_lookup, force)]
+                ex.submit(build_hostemu_shamap_nodes, force), ex.submit(build_hostemu_shamap_lookup, force),
+                ex.submit(build_hostemu_shamap_fork, force)]
         for j in jobs:
             j.result()
     build_oracle()

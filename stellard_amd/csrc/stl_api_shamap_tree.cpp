@@ -1,6 +1,7 @@
 // stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
-// ledger's changes, the inner nodes an apply makes new, lookup by key and the
-// difference of two trees): the stl_shamap_tree_* entry points of include/stl.h;
+// ledger's changes, the inner nodes an apply makes new, lookup by key, the
+// difference of two trees, the fork of one tree into another and the one-step
+// revert): the stl_shamap_tree_* entry points of include/stl.h;
 // kernels: stl_shamap_tree.hip, stl_shamap_lookup.hip, and the sort and level
 // kernels of stl_shamap.hip.
 #include "stl_host.h"
@@ -16,12 +17,17 @@ using namespace stl;
 // generation that holds the tree; an apply writes the other and the host flips
 // `live` once the apply's last enqueue has succeeded, so a failed call leaves
 // the tree as it was.  `bound`: the last count the host has read plus the rows
-// of every apply since -- never below the count on the device.
+// of every apply since -- never below the count on the device.  A fork writes
+// the other generation of its destination from the live one of its source.
 struct stl_shamap_tree {
   int ordinal = -1;
   uint32_t capacity = 0;
   int live = 0;
   uint32_t bound = 0;
+  // the one-step revert: the other generation is the tree as it was before the
+  // last successful apply or fork into it, and prev_bound the bound that went with it
+  bool revertible = false;
+  uint32_t prev_bound = 0;
   DevBuf rows[2];  // keys, then leaf hashes: 64 B per row of capacity
   DevBuf genfix;   // both generations' bucket values and meta words
   DevBuf fixed, batch, scratch;
@@ -61,13 +67,22 @@ int check_apply_args(const stl_shamap_tree* t, const void* key, const void* leaf
   return STL_OK;
 }
 
-// One apply of n >= 1 rows on stream s (g_trees.mu held, t live on d):
-// enqueued, and waited for only when the host's bound of the count no longer
-// admits the batch.  Nothing of *t changes here; the caller commits.
-int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf, const uint8_t* d_op,
-                 size_t n, uint8_t* d_root, uint32_t* d_counts, hipStream_t s, uint32_t* bound,
+int check_fork_args(const stl_shamap_tree* src, const stl_shamap_tree* dst, const void* key, const void* leaf,
+                    size_t n, const void* root, const void* counts, bool device_form) {
+  if (!src || src == dst) return STL_EINVAL;
+  return check_apply_args(dst, key, leaf, n, root, counts, device_form);
+}
+
+// One batch of n >= 1 rows on stream s (g_trees.mu held, both trees live on d):
+// src's live generation read, dst's other generation written, the work areas
+// dst's and the stream context's.  src == dst is an apply, else a fork.
+// Enqueued, and waited for only when the host's bound of src's count no longer
+// admits the batch into dst.  Nothing of *dst changes here -- the caller
+// commits -- and of *src only an apply's own bound.
+int tree_enqueue(Device& d, stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* d_key, const uint8_t* d_leaf,
+                 const uint8_t* d_op, size_t n, uint8_t* d_root, uint32_t* d_counts, hipStream_t s, uint32_t* bound,
                  const ShamapEmit* emit = nullptr) {
-  const bool fits = (uint64_t)t->bound + n <= t->capacity;
+  const bool fits = (uint64_t)src->bound + n <= dst->capacity;
   size_t temp = 0, temp_buckets = 0;
   STL_TRY(stl::shamap_temp_bytes(n, &temp));
   STL_TRY(stl::shamap_temp_bytes(stl::kTreeBuckets, &temp_buckets));
@@ -75,16 +90,17 @@ int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint
   const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
   std::lock_guard<std::mutex> lk(c->mu);
   STL_RC(c->shamap.ensure(stl::shamap_workspace_bytes(n, temp)));
-  STL_RC(t->batch.ensure(stl::shamap_tree_batch_bytes(n)));
+  STL_RC(dst->batch.ensure(stl::shamap_tree_batch_bytes(n)));
   stl::TreeApply a;
-  a.from = t->gen(t->live);
-  a.to = t->gen(t->live ^ 1);
-  a.capacity = t->capacity;
-  a.items_bound = t->bound;
-  a.after_bound = fits ? t->bound + (uint32_t)n : t->capacity;
-  a.fixed = t->fixed.p;
-  a.batch = t->batch.p;
-  a.scratch = t->scratch.p;
+  a.from = src->gen(src->live);
+  a.to = dst->gen(dst->live ^ 1);
+  a.capacity = dst->capacity;
+  a.from_capacity = src->capacity;
+  a.items_bound = src->bound;
+  a.after_bound = fits ? src->bound + (uint32_t)n : dst->capacity;
+  a.fixed = dst->fixed.p;
+  a.batch = dst->batch.p;
+  a.scratch = dst->scratch.p;
   a.sort_ws = c->shamap.p;
   a.temp_bytes = temp;
   STL_TRY(stl::launch_shamap_tree_locate(a, d_key, d_leaf, d_op, (uint32_t)n, fault_now, phase_clock(d), s));
@@ -94,25 +110,131 @@ int tree_enqueue(Device& d, stl_shamap_tree* t, const uint8_t* d_key, const uint
     // written so far, so a refusal leaves the tree as it was.
     uint32_t count = 0, cc[4] = {};
     STL_TRY(hipMemcpyAsync(&count, a.from.meta, 4, hipMemcpyDeviceToHost, s));
-    STL_TRY(hipMemcpyAsync(cc, stl::shamap_tree_change_counts(t->fixed.p), sizeof(cc), hipMemcpyDeviceToHost, s));
+    STL_TRY(hipMemcpyAsync(cc, stl::shamap_tree_change_counts(dst->fixed.p), sizeof(cc), hipMemcpyDeviceToHost, s));
     STL_TRY(hipStreamSynchronize(s));
-    if (count > t->bound || cc[3] > count || cc[1] > n) return STL_EHIP;
-    t->bound = count;
+    if (count > src->bound || cc[3] > count || cc[1] > n) return STL_EHIP;
+    if (src == dst) src->bound = count;  // a fork only reads its source, the host's bound included
     const uint64_t after = (uint64_t)count - cc[3] + cc[1];
-    if (after > t->capacity) return STL_ENOMEM;
+    if (after > dst->capacity) return STL_ENOMEM;
     a.items_bound = count;
     a.after_bound = after ? (uint32_t)after : 1u;
     *bound = (uint32_t)after;
   } else {
-    *bound = t->bound + (uint32_t)n;
+    *bound = src->bound + (uint32_t)n;
   }
   STL_TRY(stl::launch_shamap_tree_merge(a, (uint32_t)n, d_root, d_counts, fault_now, phase_clock(d), s, emit));
   return STL_OK;
 }
 
+// The fork of no rows (g_trees.mu held, both trees live on d): src's live
+// generation copied into dst's other one.  As tree_enqueue: no wait while src's
+// bound fits dst, else the one wait for the exact count.
+int snapshot_enqueue(const stl_shamap_tree* src, const stl_shamap_tree* dst, uint8_t* d_root, uint32_t* d_counts,
+                     uint32_t* d_node_count, hipStream_t s, uint32_t* bound) {
+  const stl::TreeGen from = src->gen(src->live);
+  uint32_t items = src->bound;
+  if (items > dst->capacity) {
+    STL_TRY(hipMemcpyAsync(&items, from.meta, 4, hipMemcpyDeviceToHost, s));
+    STL_TRY(hipStreamSynchronize(s));
+    if (items > src->bound) return STL_EHIP;
+    if (items > dst->capacity) return STL_ENOMEM;
+  }
+  *bound = items;
+  STL_TRY(stl::launch_shamap_tree_snapshot(from, src->capacity, items, dst->gen(dst->live ^ 1), dst->capacity, d_root,
+                                           d_counts, d_node_count, fault_now, s));
+  return STL_OK;
+}
+
+// The turn to the generation just written; what a revert needs is kept.
 void tree_commit(stl_shamap_tree* t, uint32_t bound_after) {
+  t->prev_bound = t->bound;
   t->live ^= 1;
   t->bound = bound_after;
+  t->revertible = true;
+}
+
+// A call into t failed past its argument checks: the other generation -- the
+// one a revert would turn back to -- may be half written.  The tree itself is as
+// it was; a revert is refused until the next successful apply or fork into t.
+void tree_failed(stl_shamap_tree* t) { t->revertible = false; }
+
+// Both handles live and on the calling thread's device (g_trees.mu held).
+int trees_for_call(const stl_shamap_tree* a, const stl_shamap_tree* b, Device** d);
+
+// What the apply and fork entry points share.  src == dst: an apply of the
+// batch to the tree; else a fork of src into dst.  out: the nodes form's
+// arrays, or null.  A fork of no rows is the snapshot; an apply of no rows
+// reports and changes nothing.
+int batch_device(stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* d_key, const uint8_t* d_leaf,
+                 const uint8_t* d_op, size_t n, uint8_t* d_root, uint32_t* d_counts, const stl_shamap_nodes_out* out,
+                 void* stream) {
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(trees_for_call(src, dst, &d));
+  if (n > dst->capacity) return STL_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint32_t* const d_node_count = out ? out->count : nullptr;
+  if (n == 0 && src == dst) {
+    STL_TRY(stl::launch_shamap_tree_report(dst->gen(dst->live), d_root, d_counts, s, d_node_count));
+    return STL_OK;
+  }
+  uint32_t bound = 0;
+  int rc;
+  if (n == 0) {
+    rc = snapshot_enqueue(src, dst, d_root, d_counts, d_node_count, s, &bound);
+  } else if (out) {
+    const ShamapEmit emit = emit_of(*out);
+    rc = tree_enqueue(*d, src, dst, d_key, d_leaf, d_op, n, d_root, d_counts, s, &bound, &emit);
+  } else {
+    rc = tree_enqueue(*d, src, dst, d_key, d_leaf, d_op, n, d_root, d_counts, s, &bound);
+  }
+  if (rc) {
+    tree_failed(dst);
+    return rc;
+  }
+  tree_commit(dst, bound);
+  return STL_OK;
+}
+
+int batch_host(const char* name, stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* key, const uint8_t* leaf,
+               const uint8_t* op, size_t n, uint8_t root[32], uint32_t counts[8], const stl_shamap_nodes_out* out) {
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(trees_for_call(src, dst, &dp));
+  if (n > dst->capacity) return STL_EINVAL;
+  const bool report = n == 0 && src == dst;
+  uint32_t bound = 0;
+  HostCall call(name, n, *dp);
+  const int rc = call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(d.txid.ensure(32));
+    STL_RC(d.status.ensure(32));
+    NodeStage stage;
+    if (out) STL_RC(stage.ensure(d, *out));
+    uint8_t* d_root = static_cast<uint8_t*>(d.txid.p);
+    uint32_t* d_counts = static_cast<uint32_t*>(d.status.p);
+    uint32_t* const d_node_count = out ? stage.emit.count : nullptr;
+    if (report) {
+      STL_TRY(stl::launch_shamap_tree_report(dst->gen(dst->live), d_root, d_counts, d.stream, d_node_count));
+    } else if (n == 0) {
+      STL_RC(snapshot_enqueue(src, dst, d_root, d_counts, d_node_count, d.stream, &bound));
+    } else {
+      STL_RC(call.upload(d.pk, key, n * 32));
+      if (leaf) STL_RC(call.upload(d.msg, leaf, n * 32));
+      if (op) STL_RC(call.upload(d.sig, op, n));
+      STL_RC(tree_enqueue(d, src, dst, static_cast<const uint8_t*>(d.pk.p),
+                          leaf ? static_cast<const uint8_t*>(d.msg.p) : nullptr,
+                          op ? static_cast<const uint8_t*>(d.sig.p) : nullptr, n, d_root, d_counts, d.stream, &bound,
+                          out ? &stage.emit : nullptr));
+    }
+    call.download(root, d.txid, 32);
+    call.download(counts, d.status, 32);
+    return out ? stage.fetch(call, *out) : STL_OK;
+  });
+  if (report) return rc;
+  if (rc == STL_OK) tree_commit(dst, bound);  // only once the results are back
+  else tree_failed(dst);
+  return rc;
 }
 
 // ---- the read-only calls: nothing below changes *t ----
@@ -149,7 +271,6 @@ int check_compare_args(const stl_shamap_tree* a, const stl_shamap_tree* b, const
   return STL_OK;
 }
 
-// Both handles live and on the calling thread's device (g_trees.mu held).
 int trees_for_call(const stl_shamap_tree* a, const stl_shamap_tree* b, Device** d) {
   if (!g_trees.live(a) || !g_trees.live(b)) return STL_EINVAL;
   STL_RC(g_trees.for_call(a, d));
@@ -233,52 +354,13 @@ int stl_shamap_tree_get_info(stl_shamap_tree* t, stl_shamap_tree_info* out) {
 int stl_shamap_tree_apply_device(stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf_hash,
                                  const uint8_t* d_op, size_t n, uint8_t* d_root, uint32_t* d_counts, void* stream) {
   STL_RC(check_apply_args(t, d_key, d_leaf_hash, n, d_root, d_counts, true));
-  std::lock_guard<std::mutex> lk(g_trees.mu);
-  Device* d = nullptr;
-  STL_RC(g_trees.for_call(t, &d));
-  if (n > t->capacity) return STL_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, s));
-    return STL_OK;
-  }
-  uint32_t bound = 0;
-  STL_RC(tree_enqueue(*d, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, s, &bound));
-  tree_commit(t, bound);
-  return STL_OK;
+  return batch_device(t, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, nullptr, stream);
 }
 
 int stl_shamap_tree_apply(stl_shamap_tree* t, const uint8_t* key, const uint8_t* leaf_hash, const uint8_t* op,
                           size_t n, uint8_t root[32], uint32_t counts[8]) {
   STL_RC(check_apply_args(t, key, leaf_hash, n, root, counts, false));
-  std::lock_guard<std::mutex> lk(g_trees.mu);
-  Device* dp = nullptr;
-  STL_RC(g_trees.for_call(t, &dp));
-  if (n > t->capacity) return STL_EINVAL;
-  uint32_t bound = 0;
-  HostCall call("stl_shamap_tree_apply", n, *dp);
-  const int rc = call.run([&]() -> int {
-    Device& d = call.d;
-    STL_RC(d.txid.ensure(32));
-    STL_RC(d.status.ensure(32));
-    uint8_t* d_root = static_cast<uint8_t*>(d.txid.p);
-    uint32_t* d_counts = static_cast<uint32_t*>(d.status.p);
-    if (n == 0) {
-      STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, d.stream));
-    } else {
-      STL_RC(call.upload(d.pk, key, n * 32));
-      if (leaf_hash) STL_RC(call.upload(d.msg, leaf_hash, n * 32));
-      if (op) STL_RC(call.upload(d.sig, op, n));
-      STL_RC(tree_enqueue(d, t, static_cast<const uint8_t*>(d.pk.p),
-                          leaf_hash ? static_cast<const uint8_t*>(d.msg.p) : nullptr,
-                          op ? static_cast<const uint8_t*>(d.sig.p) : nullptr, n, d_root, d_counts, d.stream, &bound));
-    }
-    call.download(root, d.txid, 32);
-    call.download(counts, d.status, 32);
-    return STL_OK;
-  });
-  if (rc == STL_OK && n) tree_commit(t, bound);  // only once the results are back
-  return rc;
+  return batch_host("stl_shamap_tree_apply", t, t, key, leaf_hash, op, n, root, counts, nullptr);
 }
 
 int stl_shamap_tree_apply_nodes_device(stl_shamap_tree* t, const uint8_t* d_key, const uint8_t* d_leaf_hash,
@@ -286,57 +368,54 @@ int stl_shamap_tree_apply_nodes_device(stl_shamap_tree* t, const uint8_t* d_key,
                                        const stl_shamap_nodes_out* out, void* stream) {
   STL_RC(check_apply_args(t, d_key, d_leaf_hash, n, d_root, d_counts, true));
   STL_RC(check_nodes_out(out, true));
-  std::lock_guard<std::mutex> lk(g_trees.mu);
-  Device* d = nullptr;
-  STL_RC(g_trees.for_call(t, &d));
-  if (n > t->capacity) return STL_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, s, out->count));
-    return STL_OK;
-  }
-  const ShamapEmit emit = emit_of(*out);
-  uint32_t bound = 0;
-  STL_RC(tree_enqueue(*d, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, s, &bound, &emit));
-  tree_commit(t, bound);
-  return STL_OK;
+  return batch_device(t, t, d_key, d_leaf_hash, d_op, n, d_root, d_counts, out, stream);
 }
 
 int stl_shamap_tree_apply_nodes(stl_shamap_tree* t, const uint8_t* key, const uint8_t* leaf_hash, const uint8_t* op,
                                 size_t n, uint8_t root[32], uint32_t counts[8], const stl_shamap_nodes_out* out) {
   STL_RC(check_apply_args(t, key, leaf_hash, n, root, counts, false));
   STL_RC(check_nodes_out(out, false));
+  return batch_host("stl_shamap_tree_apply_nodes", t, t, key, leaf_hash, op, n, root, counts, out);
+}
+
+int stl_shamap_tree_fork_device(stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* d_key,
+                                const uint8_t* d_leaf_hash, const uint8_t* d_op, size_t n, uint8_t* d_root,
+                                uint32_t* d_counts, void* stream) {
+  STL_RC(check_fork_args(src, dst, d_key, d_leaf_hash, n, d_root, d_counts, true));
+  return batch_device(src, dst, d_key, d_leaf_hash, d_op, n, d_root, d_counts, nullptr, stream);
+}
+
+int stl_shamap_tree_fork(stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* key, const uint8_t* leaf_hash,
+                         const uint8_t* op, size_t n, uint8_t root[32], uint32_t counts[8]) {
+  STL_RC(check_fork_args(src, dst, key, leaf_hash, n, root, counts, false));
+  return batch_host("stl_shamap_tree_fork", src, dst, key, leaf_hash, op, n, root, counts, nullptr);
+}
+
+int stl_shamap_tree_fork_nodes_device(stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* d_key,
+                                      const uint8_t* d_leaf_hash, const uint8_t* d_op, size_t n, uint8_t* d_root,
+                                      uint32_t* d_counts, const stl_shamap_nodes_out* out, void* stream) {
+  STL_RC(check_fork_args(src, dst, d_key, d_leaf_hash, n, d_root, d_counts, true));
+  STL_RC(check_nodes_out(out, true));
+  return batch_device(src, dst, d_key, d_leaf_hash, d_op, n, d_root, d_counts, out, stream);
+}
+
+int stl_shamap_tree_fork_nodes(stl_shamap_tree* src, stl_shamap_tree* dst, const uint8_t* key,
+                               const uint8_t* leaf_hash, const uint8_t* op, size_t n, uint8_t root[32],
+                               uint32_t counts[8], const stl_shamap_nodes_out* out) {
+  STL_RC(check_fork_args(src, dst, key, leaf_hash, n, root, counts, false));
+  STL_RC(check_nodes_out(out, false));
+  return batch_host("stl_shamap_tree_fork_nodes", src, dst, key, leaf_hash, op, n, root, counts, out);
+}
+
+int stl_shamap_tree_revert(stl_shamap_tree* t) {
   std::lock_guard<std::mutex> lk(g_trees.mu);
-  Device* dp = nullptr;
-  STL_RC(g_trees.for_call(t, &dp));
-  if (n > t->capacity) return STL_EINVAL;
-  uint32_t bound = 0;
-  HostCall call("stl_shamap_tree_apply_nodes", n, *dp);
-  const int rc = call.run([&]() -> int {
-    Device& d = call.d;
-    STL_RC(d.txid.ensure(32));
-    STL_RC(d.status.ensure(32));
-    NodeStage stage;
-    STL_RC(stage.ensure(d, *out));
-    uint8_t* d_root = static_cast<uint8_t*>(d.txid.p);
-    uint32_t* d_counts = static_cast<uint32_t*>(d.status.p);
-    if (n == 0) {
-      STL_TRY(stl::launch_shamap_tree_report(t->gen(t->live), d_root, d_counts, d.stream, stage.emit.count));
-    } else {
-      STL_RC(call.upload(d.pk, key, n * 32));
-      if (leaf_hash) STL_RC(call.upload(d.msg, leaf_hash, n * 32));
-      if (op) STL_RC(call.upload(d.sig, op, n));
-      STL_RC(tree_enqueue(d, t, static_cast<const uint8_t*>(d.pk.p),
-                          leaf_hash ? static_cast<const uint8_t*>(d.msg.p) : nullptr,
-                          op ? static_cast<const uint8_t*>(d.sig.p) : nullptr, n, d_root, d_counts, d.stream, &bound,
-                          &stage.emit));
-    }
-    call.download(root, d.txid, 32);
-    call.download(counts, d.status, 32);
-    return stage.fetch(call, *out);
-  });
-  if (rc == STL_OK && n) tree_commit(t, bound);  // only once the results are back
-  return rc;
+  if (!g_trees.live(t)) return STL_EINVAL;
+  // one step, and only to a generation that a successful call left whole
+  if (!t->revertible) return STL_EINVAL;
+  t->live ^= 1;
+  t->bound = t->prev_bound;
+  t->revertible = false;
+  return STL_OK;
 }
 
 int stl_shamap_tree_root_device(stl_shamap_tree* t, uint8_t* d_root, void* stream) {

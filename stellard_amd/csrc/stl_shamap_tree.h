@@ -38,9 +38,10 @@ size_t shamap_tree_batch_bytes(size_t n);
 size_t shamap_tree_scratch_bytes(size_t capacity);
 
 struct TreeApply {
-  TreeGen from, to;        // the live generation (read) and the other one (written)
-  uint32_t capacity;
-  uint32_t items_bound;    // host-known bound of the live generation's count: sizes the grids
+  TreeGen from, to;        // the generation read and the one written: of one tree (an apply) or of two (a fork)
+  uint32_t capacity;       // of the tree written: guards every store, sizes the scratch
+  uint32_t from_capacity;  // of the tree read: clamps every read of `from` (shamap_tree_readable)
+  uint32_t items_bound;    // host-known bound of the read generation's count: sizes the grids
   uint32_t after_bound;    // ... and of the count after the batch (the merge part), 1 .. capacity
   void* fixed;
   void* batch;
@@ -72,6 +73,14 @@ hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* roo
 // zeros; node_count (or null) <- zero: no node is stored.
 hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* counts, hipStream_t stream,
                                      uint32_t* node_count = nullptr);
+// The snapshot: `from` (of a tree of from_capacity, its count at most
+// items_bound <= capacity) copied into `to` (of a tree of `capacity`) -- rows by
+// the count read on the device, the bucket values and the meta words -- and a
+// finish launch that writes root, counts and node_count as the report does.
+// Two launches, no sort, no hash, no host wait.
+hipError_t launch_shamap_tree_snapshot(const TreeGen& from, uint32_t from_capacity, uint32_t items_bound,
+                                       const TreeGen& to, uint32_t capacity, uint8_t* root, uint32_t* counts,
+                                       uint32_t* node_count, bool (*fault)(), hipStream_t stream);
 // The generation's sorted content -> key / leaf (either may be null) of `rows`
 // rows, items_bound <= rows; *items (or null) <- the count.
 hipError_t launch_shamap_tree_export(const TreeGen& g, uint32_t items_bound, uint8_t* key, uint8_t* leaf,

@@ -3,7 +3,7 @@
 // batch of changes (set or delete per row) is merged in, and only the buckets
 // the batch touches are rehashed (stl_shamap_tree_core.h has the rules).
 //
-// One apply, all on the caller's stream, the live generation read and the other written:
+// One apply, all on the caller's stream, one generation read and another written:
 //   1. changes   the batch's keys through the sort passes of stl_shamap.hip;
 //                the last of equal keys is a change (head rule, scan, compact)
 //   2. locate    one lane per change bisects the resident keys: position, found,
@@ -24,6 +24,12 @@
 // Every count is read on the device; the grids come from host-known bounds
 // (rows of the batch, a bound of the item count).  Every store into a
 // generation or the scratch is guarded by the capacity.
+//
+// A fork (stl_shamap_tree_fork*) is the same sequence with the generation read
+// belonging to another tree than the one written: every read of `from` is
+// clamped by that tree's capacity (shamap_tree_readable), every store guarded by
+// the written tree's, and the work areas are the written tree's.  A fork of no
+// rows is tree_snapshot_kernel: a copy by the count, nothing sorted or hashed.
 #include "stl_shamap_tree.h"
 
 #include "stl_shamap.h"
@@ -158,14 +164,14 @@ __global__ __launch_bounds__(kTrBlock) void tree_compact_kernel(
 
 // 2. position, found and delta of every change; its bucket becomes dirty.
 __global__ __launch_bounds__(kTrBlock) void tree_locate_kernel(const uint8_t* __restrict__ rkey,
-                                                               const uint32_t* __restrict__ meta, uint32_t cap,
+                                                               const uint32_t* __restrict__ meta, uint32_t from_cap,
                                                                const uint8_t* __restrict__ ckey,
                                                                uint8_t* __restrict__ code, uint32_t n,
                                                                uint32_t* __restrict__ pos, uint32_t* __restrict__ delta,
                                                                uint32_t* __restrict__ dirty, uint32_t* wh) {
   const uint32_t j = blockIdx.x * kTrBlock + threadIdx.x;
   const uint32_t k = wh[kWhChanges] < n ? wh[kWhChanges] : n;
-  const uint32_t m = meta[0] < cap ? meta[0] : cap;
+  const uint32_t m = shamap_tree_readable(meta[0], from_cap);
   bool ins = false, rep = false, del = false, absent = false;
   if (j < k) {
     uint32_t key[8];
@@ -192,12 +198,12 @@ __global__ __launch_bounds__(kTrBlock) void tree_locate_kernel(const uint8_t* __
 
 // 3a. resident item i -> its place in the other generation.
 __global__ __launch_bounds__(kTrBlock) void tree_merge_items_kernel(
-    const uint8_t* __restrict__ rkey, const uint8_t* __restrict__ rleaf, const uint32_t* __restrict__ meta, uint32_t cap,
-    const uint32_t* __restrict__ pos, const uint8_t* __restrict__ code, const uint32_t* __restrict__ scan,
-    const uint8_t* __restrict__ cleaf, const uint32_t* __restrict__ wh, uint32_t n, uint8_t* __restrict__ nkey,
-    uint8_t* __restrict__ nleaf) {
+    const uint8_t* __restrict__ rkey, const uint8_t* __restrict__ rleaf, const uint32_t* __restrict__ meta,
+    uint32_t from_cap, uint32_t cap, const uint32_t* __restrict__ pos, const uint8_t* __restrict__ code,
+    const uint32_t* __restrict__ scan, const uint8_t* __restrict__ cleaf, const uint32_t* __restrict__ wh, uint32_t n,
+    uint8_t* __restrict__ nkey, uint8_t* __restrict__ nleaf) {
   const uint32_t i = blockIdx.x * kTrBlock + threadIdx.x;
-  const uint32_t m = meta[0] < cap ? meta[0] : cap;
+  const uint32_t m = shamap_tree_readable(meta[0], from_cap);
   if (i >= m) return;
   const uint32_t k = wh[kWhChanges] < n ? wh[kWhChanges] : n;
   bool hit = false;
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(kTrBlock) void tree_merge_items_kernel(
   if (hit && (code[r] & kTreeOpDelete)) return;
   const uint32_t before = r < k ? scan[r] : wh[kWhInserted] - wh[kWhDeleted];
   const uint32_t dst = shamap_tree_item_dest(i, before);
-  if (dst >= cap) return;  // never: the host admits a batch only when bound + n <= capacity
+  if (dst >= cap) return;  // never: the host admits a batch only when bound + n <= the written tree's capacity
   uint32_t v[8];
   shamap_load_key(v, rkey, i);
   tr_st8(nkey, dst, v);
@@ -234,11 +240,11 @@ __global__ __launch_bounds__(kTrBlock) void tree_merge_changes_kernel(
 __global__ __launch_bounds__(kTrBlock) void tree_bounds_kernel(const uint8_t* __restrict__ nkey,
                                                                const uint32_t* __restrict__ meta_from,
                                                                uint32_t* __restrict__ meta_to,
-                                                               const uint32_t* __restrict__ wh, uint32_t cap,
-                                                               uint32_t* __restrict__ lb) {
+                                                               const uint32_t* __restrict__ wh, uint32_t from_cap,
+                                                               uint32_t cap, uint32_t* __restrict__ lb) {
   const uint32_t b = blockIdx.x * kTrBlock + threadIdx.x;
   if (b > kTreeBuckets) return;
-  uint32_t m = meta_from[0] + wh[kWhInserted] - wh[kWhDeleted];
+  uint32_t m = shamap_tree_readable(meta_from[0], from_cap) + wh[kWhInserted] - wh[kWhDeleted];
   if (m > cap) m = cap;  // never
   lb[b] = shamap_tree_bucket_begin(nkey, m, b);
   if (b == 0) meta_to[0] = m;
@@ -290,6 +296,7 @@ __global__ __launch_bounds__(kTrBlock) void tree_bucket_kernel(const uint32_t* _
                                                                const uint32_t* __restrict__ sz,
                                                                const uint32_t* __restrict__ off,
                                                                const uint8_t* __restrict__ slot, uint32_t cap,
+                                                               uint32_t from_cap,
                                                                const uint32_t* __restrict__ from_cnt,
                                                                const uint32_t* __restrict__ from_h,
                                                                uint32_t* __restrict__ to_cnt,
@@ -300,7 +307,7 @@ __global__ __launch_bounds__(kTrBlock) void tree_bucket_kernel(const uint32_t* _
     c = sz[b];
     if (c && off[b] < cap) shamap_load_key(h, slot, off[b]);
   } else {
-    c = from_cnt[b];
+    c = shamap_tree_readable(from_cnt[b], from_cap);  // a clean bucket holds what it held
     shamap_load_key(h, reinterpret_cast<const uint8_t*>(from_h), b);
   }
   to_cnt[b] = c;
@@ -396,6 +403,32 @@ __global__ __launch_bounds__(kTrBlock) void tree_export_kernel(const uint8_t* __
   }
 }
 
+// The snapshot (a fork of no rows): one generation copied into another tree's,
+// in 16-byte units, lane t the t-th unit of each array -- a wave's load or store
+// is 1 KiB in a row.  The keys and the leaf hashes follow the count read here
+// (two units per row), under the source's clamp and the destination's guard;
+// the bucket values are 16,384 + 131,072 units, the meta words four, and word 0
+// of those is the count that was copied.
+constexpr uint32_t kSnapFixedUnits = 2 * kTreeBuckets;
+__global__ __launch_bounds__(kTrBlock) void tree_snapshot_kernel(TreeGen from, uint32_t from_cap, TreeGen to,
+                                                                 uint32_t cap) {
+  const uint32_t t = blockIdx.x * kTrBlock + threadIdx.x;
+  const uint32_t m = shamap_tree_snapshot_rows(from.meta[0], from_cap, cap);
+  if (t < 2 * m) {
+    const uint4 k = reinterpret_cast<const uint4*>(from.key)[t];
+    const uint4 l = reinterpret_cast<const uint4*>(from.leaf)[t];
+    reinterpret_cast<uint4*>(to.key)[t] = k;
+    reinterpret_cast<uint4*>(to.leaf)[t] = l;
+  }
+  if (t < kSnapFixedUnits) reinterpret_cast<uint4*>(to.bh)[t] = reinterpret_cast<const uint4*>(from.bh)[t];
+  if (t < kTreeBuckets / 4) reinterpret_cast<uint4*>(to.bcnt)[t] = reinterpret_cast<const uint4*>(from.bcnt)[t];
+  if (t < kTreeMetaWords / 4) {
+    uint4 w = reinterpret_cast<const uint4*>(from.meta)[t];
+    if (t == 0) w.x = m;
+    reinterpret_cast<uint4*>(to.meta)[t] = w;
+  }
+}
+
 }  // namespace
 
 size_t shamap_tree_gen_fixed_bytes() { return up256(4 * kTreeBuckets) + up256(32 * kTreeBuckets) + up256(4 * kTreeMetaWords); }
@@ -428,10 +461,11 @@ hipError_t launch_shamap_tree_locate(const TreeApply& a, const uint8_t* key, con
                                      uint32_t n, bool (*fault)(), const PhaseClock* clock, hipStream_t stream) {
   if (n == 0 || !key || !a.fixed || !a.batch || !a.scratch || !a.sort_ws) return hipErrorInvalidValue;
   if (((uintptr_t)key & 15u) || ((uintptr_t)leaf & 15u)) return hipErrorInvalidValue;
-  if (a.capacity == 0 || a.items_bound > a.capacity || n > a.capacity) return hipErrorInvalidValue;
+  if (a.capacity == 0 || a.from_capacity == 0 || a.items_bound > a.from_capacity || n > a.capacity)
+    return hipErrorInvalidValue;
   const TreeFixed f(a.fixed);
   const TreeBatch b(a.batch, n);
-  const uint32_t cap = a.capacity, gn = grid_of(n);
+  const uint32_t gn = grid_of(n);
   if (clock) clock->mark(clock->ctx, stream, 0);
   TR_TRY(hipMemsetAsync(f.wh, 0, (size_t)(reinterpret_cast<uint8_t*>(f.dirty) - reinterpret_cast<uint8_t*>(f.wh)) +
                                      4 * kTreeBuckets, stream));
@@ -443,8 +477,8 @@ hipError_t launch_shamap_tree_locate(const TreeApply& a, const uint8_t* key, con
   TR_LAUNCH(tree_compact_kernel, gn, kTrBlock, key, leaf, op, so.perm, so.flags, so.idx, n, b.ckey, b.cleaf, b.code,
             f.wh);
   // 2. locate
-  TR_LAUNCH(tree_locate_kernel, gn, kTrBlock, a.from.key, a.from.meta, cap, b.ckey, b.code, n, b.pos, b.delta, f.dirty,
-            f.wh);
+  TR_LAUNCH(tree_locate_kernel, gn, kTrBlock, a.from.key, a.from.meta, a.from_capacity, b.ckey, b.code, n, b.pos,
+            b.delta, f.dirty, f.wh);
   TR_RC(shamap_exclusive_scan(so.temp, a.temp_bytes, b.delta, b.scan, n, fault, stream));
   if (clock) clock->mark(clock->ctx, stream, 1);
   return hipSuccess;
@@ -456,23 +490,24 @@ hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* roo
                                     const PhaseClock* clock, hipStream_t stream, const ShamapEmit* emit) {
   if (n == 0 || !root || !a.fixed || !a.batch || !a.scratch || !a.sort_ws) return hipErrorInvalidValue;
   if (((uintptr_t)root & 3u) || ((uintptr_t)counts & 3u)) return hipErrorInvalidValue;
-  if (a.capacity == 0 || a.items_bound > a.capacity || a.after_bound > a.capacity || a.after_bound == 0)
+  if (a.capacity == 0 || a.from_capacity == 0 || a.items_bound > a.from_capacity || a.after_bound > a.capacity ||
+      a.after_bound == 0)
     return hipErrorInvalidValue;
   const TreeFixed f(a.fixed);
   const TreeBatch b(a.batch, n);
   const TreeScratch s(a.scratch, a.capacity);
-  const uint32_t cap = a.capacity, after = a.after_bound;
+  const uint32_t cap = a.capacity, from_cap = a.from_capacity, after = a.after_bound;
   const uint32_t gn = grid_of(n), gb = kTreeBuckets / kTrBlock;
   void* temp = shamap_workspace_temp(n, a.sort_ws, a.temp_bytes);
   // 3. merge
   if (a.items_bound)
-    TR_LAUNCH(tree_merge_items_kernel, grid_of(a.items_bound), kTrBlock, a.from.key, a.from.leaf, a.from.meta, cap,
-              b.pos, b.code, b.scan, b.cleaf, f.wh, n, a.to.key, a.to.leaf);
+    TR_LAUNCH(tree_merge_items_kernel, grid_of(a.items_bound), kTrBlock, a.from.key, a.from.leaf, a.from.meta,
+              from_cap, cap, b.pos, b.code, b.scan, b.cleaf, f.wh, n, a.to.key, a.to.leaf);
   TR_LAUNCH(tree_merge_changes_kernel, gn, kTrBlock, b.ckey, b.cleaf, b.code, b.pos, b.scan, f.wh, n, cap, a.to.key,
             a.to.leaf);
   if (clock) clock->mark(clock->ctx, stream, 2);
   // 4. bounds
-  TR_LAUNCH(tree_bounds_kernel, gb + 1, kTrBlock, a.to.key, a.from.meta, a.to.meta, f.wh, cap, f.lb);
+  TR_LAUNCH(tree_bounds_kernel, gb + 1, kTrBlock, a.to.key, a.from.meta, a.to.meta, f.wh, from_cap, cap, f.lb);
   // 5. subtrees
   TR_LAUNCH(tree_sizes_kernel, gb, kTrBlock, f.dirty, f.lb, f.sz, f.wh);
   TR_RC(shamap_exclusive_scan(temp, a.temp_bytes, f.sz, f.off, kTreeBuckets, fault, stream));
@@ -483,8 +518,8 @@ hipError_t launch_shamap_tree_merge(const TreeApply& a, uint32_t n, uint8_t* roo
                              emit));
   if (clock) clock->mark(clock->ctx, stream, 3);
   // 6. bucket values and top
-  TR_LAUNCH(tree_bucket_kernel, gb, kTrBlock, f.dirty, f.sz, f.off, s.slot, cap, a.from.bcnt, a.from.bh, a.to.bcnt,
-            a.to.bh);
+  TR_LAUNCH(tree_bucket_kernel, gb, kTrBlock, f.dirty, f.sz, f.off, s.slot, cap, from_cap, a.from.bcnt, a.from.bh,
+            a.to.bcnt, a.to.bh);
   uint32_t* const no_words = nullptr;
   if (emit) {
     // the same four launches, storing: the row numbers go on from where the scratch's level launches stopped
@@ -524,6 +559,21 @@ hipError_t launch_shamap_tree_report(const TreeGen& g, uint8_t* root, uint32_t* 
   hipLaunchKernelGGL(tree_finish_kernel, dim3(1), dim3(64), 0, stream, g.meta, static_cast<const uint32_t*>(nullptr), 0u,
                      reinterpret_cast<uint32_t*>(root), counts, static_cast<const uint32_t*>(nullptr), node_count);
   return hipGetLastError();
+}
+
+hipError_t launch_shamap_tree_snapshot(const TreeGen& from, uint32_t from_capacity, uint32_t items_bound,
+                                       const TreeGen& to, uint32_t capacity, uint8_t* root, uint32_t* counts,
+                                       uint32_t* node_count, bool (*fault)(), hipStream_t stream) {
+  if (!root || ((uintptr_t)root & 3u) || ((uintptr_t)counts & 3u) || ((uintptr_t)node_count & 3u))
+    return hipErrorInvalidValue;
+  if (capacity == 0 || from_capacity == 0 || items_bound > from_capacity || items_bound > capacity)
+    return hipErrorInvalidValue;
+  const uint32_t units = 2 * items_bound > kSnapFixedUnits ? 2 * items_bound : kSnapFixedUnits;
+  TR_LAUNCH(tree_snapshot_kernel, grid_of(units), kTrBlock, from, from_capacity, to, capacity);
+  const uint32_t* const no_words = nullptr;
+  TR_LAUNCH(tree_finish_kernel, 1, 64, to.meta, no_words, 0u, reinterpret_cast<uint32_t*>(root), counts, no_words,
+            node_count);
+  return hipSuccess;
 }
 
 hipError_t launch_shamap_tree_export(const TreeGen& g, uint32_t items_bound, uint8_t* key, uint8_t* leaf,

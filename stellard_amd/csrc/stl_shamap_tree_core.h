@@ -30,6 +30,21 @@ STL_HD uint32_t shamap_tree_bucket(const uint32_t key[kShamapKeyWords]) {
   return ((key[0] & 0xffu) << 8) | ((key[0] >> 8) & 0xffu);
 }
 
+// How many rows of a generation may be read: its stated count, and never more
+// than the capacity its arrays were made for.  A fork reads one tree's
+// generation and writes another's, so the reading side has a capacity of its
+// own; every read of `from` goes by this, every store by the writing side's.
+STL_HD uint32_t shamap_tree_readable(uint32_t stated_count, uint32_t from_capacity) {
+  return stated_count < from_capacity ? stated_count : from_capacity;
+}
+
+// The rows a snapshot copies: what may be read, and never more than the
+// written side holds (the host refuses a snapshot that would not fit).
+STL_HD uint32_t shamap_tree_snapshot_rows(uint32_t stated_count, uint32_t from_capacity, uint32_t to_capacity) {
+  const uint32_t m = shamap_tree_readable(stated_count, from_capacity);
+  return m < to_capacity ? m : to_capacity;
+}
+
 // The last-of-equals head rule over the batch's sorted positions: position i
 // holds a change when the key after it differs (or there is none).  The sort is
 // stable, so of equal keys this is the highest row: the batch reads as a

@@ -871,13 +871,12 @@ class ShamapTree(_DeviceObject):
         i["root"] = bytes(i["root"])
         return i
 
-    def apply_device(self, keys, leaf_hashes=None, ops=None, out_root=None, counts=False, stream=None):
-        """stl_shamap_tree_apply_device: keys (n, 32) uint8 in HBM, leaf_hashes
-        (n, 32) or None (the leaf hash is the key), ops uint8[n] (0 set, else
-        delete) or None (all sets) -> (1, 32) uint8 root, or (root, int32[8]
-        counts) with ``counts`` (True, or a tensor to write them to).
-        Asynchronous on ``stream``."""
+    # What the apply and the fork wrappers share: `name` the entry point,
+    # `handles` the tree handles it takes first.
+    def _batch_device(self, name, handles, keys, leaf_hashes, ops, out_root, cnt, nodes, stream):
         import torch
+        if keys is None:  # a fork of no rows
+            keys = torch.empty((0, 32), dtype=torch.uint8, device="cuda")
         if keys.dim() != 2:
             raise ValueError("keys must be (n, 32) bytes")
         n = keys.shape[0]
@@ -887,25 +886,29 @@ class ShamapTree(_DeviceObject):
         if out_root is None:
             out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
         _check_hashes(1, out_root=out_root)
-        cnt = None
-        if counts is True:
+        if nodes is not None:
+            cnt = _node_counts(cnt, 8, keys.device)
+            nodes = _device_nodes(nodes[0], nodes[1], nodes[2], nodes[3], keys.device)
+        elif cnt is True:
             cnt = torch.empty(8, dtype=torch.int32, device=keys.device)
-        elif counts is not False and counts is not None:
-            cnt = counts
-            if cnt.dtype != torch.int32 or tuple(cnt.shape) != (8,):
-                raise ValueError("counts must be int32[8]")
+        elif cnt is False or cnt is None:
+            cnt = None
+        elif cnt.dtype != torch.int32 or tuple(cnt.shape) != (8,):
+            raise ValueError("counts must be int32[8]")
         for t in (keys, leaf_hashes, ops, out_root, cnt):
             if t is not None and (not t.is_cuda or not t.is_contiguous()):
                 raise ValueError("device entry point needs contiguous CUDA tensors")
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        N.check(N.load().stl_shamap_tree_apply_device(self._h, p(keys), p(leaf_hashes), p(ops), n, p(out_root), p(cnt),
-                                                      _stream_ptr(stream)), "stl_shamap_tree_apply_device")
-        return out_root if cnt is None else (out_root, cnt)
+        args = [*handles, p(keys), p(leaf_hashes), p(ops), n, p(out_root), p(cnt)]
+        if nodes is not None:
+            out = nodes.struct()
+            args.append(ctypes.byref(out))
+        N.check(getattr(N.load(), name)(*args, _stream_ptr(stream)), name)
+        return out_root, cnt, nodes
 
-    def apply(self, keys, leaf_hashes=None, ops=None, counts=False):
-        """stl_shamap_tree_apply: host memory, synchronous.  keys (n, 32) uint8,
-        leaf_hashes (n, 32) or None, ops uint8[n] or bool[n] or None -> 32 root
-        bytes, or (root, [8 counts]) with ``counts``."""
+    def _batch_host(self, name, handles, keys, leaf_hashes, ops, nodes):
+        if keys is None:  # a fork of no rows
+            keys = np.zeros((0, 32), np.uint8)
         keys = np.ascontiguousarray(keys)
         if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
             raise ValueError("keys must be (n, 32) uint8")
@@ -921,10 +924,35 @@ class ShamapTree(_DeviceObject):
             ops = ops.astype(np.uint8)
         root = np.zeros(32, dtype=np.uint8)
         cnt = np.zeros(8, dtype=np.uint32)
-        N.check(N.load().stl_shamap_tree_apply(
-            self._h, _buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n else None,
-            _buf(ops) if ops is not None and n else None, n, _buf(root), _buf(cnt)), "stl_shamap_tree_apply")
-        return (root.tobytes(), [int(x) for x in cnt]) if counts else root.tobytes()
+        args = [*handles, _buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n else None,
+                _buf(ops) if ops is not None and n else None, n, _buf(root), _buf(cnt)]
+        if nodes is not None:
+            nodes = HostNodes(*nodes)
+            out = nodes.struct()
+            args.append(ctypes.byref(out))
+        N.check(getattr(N.load(), name)(*args), name)
+        return root.tobytes(), [int(x) for x in cnt], nodes
+
+    def apply_device(self, keys, leaf_hashes=None, ops=None, out_root=None, counts=False, stream=None):
+        """stl_shamap_tree_apply_device: keys (n, 32) uint8 in HBM, leaf_hashes
+        (n, 32) or None (the leaf hash is the key), ops uint8[n] (0 set, else
+        delete) or None (all sets) -> (1, 32) uint8 root, or (root, int32[8]
+        counts) with ``counts`` (True, or a tensor to write them to).
+        Asynchronous on ``stream``."""
+        if keys is None:
+            raise ValueError("keys must be (n, 32) bytes")
+        root, cnt, _ = self._batch_device("stl_shamap_tree_apply_device", [self._h], keys, leaf_hashes, ops, out_root,
+                                          counts, None, stream)
+        return root if cnt is None else (root, cnt)
+
+    def apply(self, keys, leaf_hashes=None, ops=None, counts=False):
+        """stl_shamap_tree_apply: host memory, synchronous.  keys (n, 32) uint8,
+        leaf_hashes (n, 32) or None, ops uint8[n] or bool[n] or None -> 32 root
+        bytes, or (root, [8 counts]) with ``counts``."""
+        if keys is None:
+            raise ValueError("keys must be (n, 32) uint8")
+        root, cnt, _ = self._batch_host("stl_shamap_tree_apply", [self._h], keys, leaf_hashes, ops, None)
+        return (root, cnt) if counts else root
 
     def root_device(self, out_root=None, stream=None):
         """The current root -> (1, 32) uint8 CUDA tensor (async on ``stream``)."""
@@ -967,53 +995,60 @@ class ShamapTree(_DeviceObject):
         tree's inner nodes of the dirty buckets and of the prefixes above them
         -> (root, counts, nodes); ``nodes`` as ``shamap_nodes_device`` gives
         it.  Asynchronous on ``stream``."""
-        import torch
-        if keys.dim() != 2:
+        if keys is None:
             raise ValueError("keys must be (n, 32) bytes")
-        n = keys.shape[0]
-        _check_hashes(n, keys=keys, leaf_hashes=leaf_hashes)
-        if ops is not None and (ops.dtype != torch.uint8 or tuple(ops.shape) != (n,)):
-            raise ValueError("ops must be uint8[n]")
-        if out_root is None:
-            out_root = torch.empty((1, 32), dtype=torch.uint8, device=keys.device)
-        _check_hashes(1, out_root=out_root)
-        cnt = _node_counts(counts, 8, keys.device)
-        nodes = _device_nodes(nodes, max_nodes, ids, meta, keys.device)
-        for t in (keys, leaf_hashes, ops, out_root, cnt):
-            if t is not None and (not t.is_cuda or not t.is_contiguous()):
-                raise ValueError("device entry point needs contiguous CUDA tensors")
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        out = nodes.struct()
-        N.check(N.load().stl_shamap_tree_apply_nodes_device(self._h, p(keys), p(leaf_hashes), p(ops), n, p(out_root),
-                                                            p(cnt), ctypes.byref(out), _stream_ptr(stream)),
-                "stl_shamap_tree_apply_nodes_device")
-        return out_root, cnt, nodes
+        return self._batch_device("stl_shamap_tree_apply_nodes_device", [self._h], keys, leaf_hashes, ops, out_root,
+                                  counts, (nodes, max_nodes, ids, meta), stream)
 
     def apply_nodes(self, keys, leaf_hashes=None, ops=None, max_nodes=0, ids=True, meta=True):
         """stl_shamap_tree_apply_nodes: host memory, synchronous -> (32 root
         bytes, [8 counts], nodes); ``nodes`` as ``shamap_nodes`` gives it."""
-        keys = np.ascontiguousarray(keys)
-        if keys.dtype != np.uint8 or keys.ndim != 2 or keys.shape[1] != 32:
+        if keys is None:
             raise ValueError("keys must be (n, 32) uint8")
-        n = keys.shape[0]
-        if leaf_hashes is not None:
-            leaf_hashes = np.ascontiguousarray(leaf_hashes)
-            if leaf_hashes.dtype != np.uint8 or leaf_hashes.shape != (n, 32):
-                raise ValueError("leaf_hashes must be (n, 32) uint8")
-        if ops is not None:
-            ops = np.ascontiguousarray(ops)
-            if ops.dtype not in (np.uint8, np.bool_) or ops.shape != (n,):
-                raise ValueError("ops must be uint8[n] or bool[n]")
-            ops = ops.astype(np.uint8)
-        root = np.zeros(32, dtype=np.uint8)
-        cnt = np.zeros(8, dtype=np.uint32)
-        nodes = HostNodes(max_nodes, ids, meta)
-        out = nodes.struct()
-        N.check(N.load().stl_shamap_tree_apply_nodes(
-            self._h, _buf(keys) if n else None, _buf(leaf_hashes) if leaf_hashes is not None and n else None,
-            _buf(ops) if ops is not None and n else None, n, _buf(root), _buf(cnt), ctypes.byref(out)),
-            "stl_shamap_tree_apply_nodes")
-        return root.tobytes(), [int(x) for x in cnt], nodes
+        return self._batch_host("stl_shamap_tree_apply_nodes", [self._h], keys, leaf_hashes, ops,
+                                (max_nodes, ids, meta))
+
+    # ---- SHAMap::snapShot: a fork into another handle, and the one-step revert ----
+    def _fork_handles(self, dst):
+        if not isinstance(dst, ShamapTree):
+            raise ValueError("dst must be a ShamapTree")
+        if dst is self:
+            raise ValueError("a tree cannot be forked into itself")
+        return [self._h, dst._h]
+
+    def fork_device(self, dst, keys=None, leaf_hashes=None, ops=None, out_root=None, counts=False, stream=None):
+        """stl_shamap_tree_fork_device: ``dst`` becomes this tree's content with
+        the batch applied (``apply_device``'s arguments and results); this tree
+        is only read.  ``keys`` None: the plain snapshot.  Asynchronous on
+        ``stream``."""
+        root, cnt, _ = self._batch_device("stl_shamap_tree_fork_device", self._fork_handles(dst), keys, leaf_hashes,
+                                          ops, out_root, counts, None, stream)
+        return root if cnt is None else (root, cnt)
+
+    def fork(self, dst, keys=None, leaf_hashes=None, ops=None, counts=False):
+        """stl_shamap_tree_fork: host memory, synchronous; as ``apply``."""
+        root, cnt, _ = self._batch_host("stl_shamap_tree_fork", self._fork_handles(dst), keys, leaf_hashes, ops, None)
+        return (root, cnt) if counts else root
+
+    def fork_nodes_device(self, dst, keys=None, leaf_hashes=None, ops=None, max_nodes=None, nodes=None, ids=True,
+                          meta=True, out_root=None, counts=True, stream=None):
+        """stl_shamap_tree_fork_nodes_device: ``fork_device``, and the inner
+        nodes of ``dst``'s new tree that this tree does not have -> (root,
+        counts, nodes), as ``apply_nodes_device``."""
+        return self._batch_device("stl_shamap_tree_fork_nodes_device", self._fork_handles(dst), keys, leaf_hashes,
+                                  ops, out_root, counts, (nodes, max_nodes, ids, meta), stream)
+
+    def fork_nodes(self, dst, keys=None, leaf_hashes=None, ops=None, max_nodes=0, ids=True, meta=True):
+        """stl_shamap_tree_fork_nodes: host memory, synchronous -> (32 root
+        bytes, [8 counts], nodes), as ``apply_nodes``."""
+        return self._batch_host("stl_shamap_tree_fork_nodes", self._fork_handles(dst), keys, leaf_hashes, ops,
+                                (max_nodes, ids, meta))
+
+    def revert(self):
+        """stl_shamap_tree_revert: back to what the tree was before the last
+        successful apply or fork into it; one step, no device work.  Raises
+        where the C call gives STL_EINVAL (nothing to turn back to)."""
+        N.check(N.load().stl_shamap_tree_revert(self._h), "stl_shamap_tree_revert")
 
     def lookup_device(self, keys, out_words=None, leaf_hashes=False, positions=False, stream=None):
         """stl_shamap_tree_lookup_device: keys (n, 32) uint8 in HBM -> found
