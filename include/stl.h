@@ -1180,6 +1180,58 @@ int stl_shamap_tree_fork_nodes(stl_shamap_tree *src, stl_shamap_tree *dst, const
                                uint32_t counts[8], const stl_shamap_nodes_out *out);
 int stl_shamap_tree_revert(stl_shamap_tree *t);
 
+/* ---- resident SHAMap: SHAMap::getFetchPack between two trees ----
+ * For every peer that is catching up the reference walks back ledger by ledger and asks
+ * wantLedger's state map for getFetchPack(haveLedger's state map, ...) and its transaction map for
+ * getFetchPack(nullptr, ...) (NetworkOPs.cpp:2799-2826, SHAMapSync.cpp:609-674).  The call below is
+ * that walk's inner nodes for two resident trees.
+ * THE PACK F of `want` against `have`: every inner node of want, at its SHAMapNodeID (depth, the
+ * key's first `depth` nibbles), for which have holds no inner node at the same ID with the same
+ * hash.  That is the set the reference's walk visits: it emits a node and descends into an inner
+ * child only when !have->hasInnerNode(childID, childHash), hasInnerNode descends have by the ID and
+ * compares the hash it finds there (SHAMapSync.cpp:552-570), and a node that differs makes its
+ * parent differ.  The test is by position: a node of want whose hash have holds at another ID is in
+ * F.  have NULL or empty: F is every inner node of want.  Equal roots, want == have (allowed) or an
+ * empty want: F is empty.
+ * LEAVES are not rows of this call: the leaves of a fetch pack (!have->hasLeafNode(tag, hash)) are
+ * the rows of kind STL_SHAMAP_DIFF_A_ONLY and STL_SHAMAP_DIFF_CHANGED of
+ * stl_shamap_tree_compare_device(want, have), and with have NULL want's export.
+ * OUTPUTS: `out` as stl_shamap_nodes_device fills it -- hash, the 512-byte body, the optional id and
+ * meta word (depth and leaf mask) -- each node of F once, at an index below max_nodes only, in no
+ * particular order; *out->count = |F| whatever max_nodes is (the reference stops after `max` nodes
+ * in walk order; here the caller sees how much room a second call needs).  counts (8 words; the
+ * device form's d_counts may be NULL): [0] |F|, [1] buckets examined, [2] items of want gathered,
+ * [3] items of have gathered, [4] inner nodes of want hashed as candidates, at all depths,
+ * [5] candidates left out because have holds them ([4] - [5] == [0]), [6] items of want, [7] items
+ * of have (0 for NULL).
+ * READ-ONLY: content, count, root, host bound and revert state of both trees are unchanged whatever
+ * the call returns, and so are their work areas: everything the call writes besides the caller's
+ * arrays is the stream context's.  It may run beside lookups, compares and other fetch packs of the
+ * same trees on any streams; against an apply or a fork into either tree the caller orders it.
+ * BUCKET RULE, as the compare's: a bucket whose (count, hash) is equal in both trees is not
+ * examined -- exact when leaf hashes commit to their keys, the assumption the reference makes when
+ * it does not descend below an equal hash.  The cost follows what differs: the keys of the
+ * differing buckets of both trees are gathered and hashed level by level, have's depth d just
+ * before want's asks for it, and the 4,369 prefixes above the buckets are folded for both trees.
+ * The device form is asynchronous on `stream` and never waits on the host: every count is read on
+ * the device, grids and workspace come from the host's bounds of the two item counts.  The host
+ * form stages max_nodes * 580 bytes on the device, waits once for the count and copies back
+ * min(count, max_nodes) rows; a host array may have any alignment.
+ * FAILURE: *out->count and counts are written by the call's last kernel alone, so a call that
+ * failed has not written them; the row arrays may be partly written.
+ * Before any device work: what the node-storing calls refuse in `out`; a NULL want; a handle that
+ * is not live; trees of different devices or of another device than the calling thread's; d_counts
+ * not 4-byte aligned is STL_EINVAL.
+ * MEMORY: in the stream context 65 B per item of want's host bound plus 65 B per item of have's,
+ * 1.5 MiB of per-bucket words, both trees' 4,369 top values and the scans' temporary storage.
+ * Nothing is sized by the number of nodes.
+ * With stl_set_phase_timing on the call adds to stl_stats.phase_ns[0..2]: buckets and gather, the
+ * levels, top and finish. */
+int stl_shamap_tree_fetch_pack_device(stl_shamap_tree *want, stl_shamap_tree *have,
+                                      const stl_shamap_nodes_out *out, uint32_t *d_counts, void *stream);
+int stl_shamap_tree_fetch_pack(stl_shamap_tree *want, stl_shamap_tree *have, const stl_shamap_nodes_out *out,
+                               uint32_t counts[8]);
+
 #ifdef __cplusplus
 }
 #endif

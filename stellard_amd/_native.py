@@ -227,6 +227,8 @@ SYMBOLS = [
      [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P, _P]),
     ("stl_shamap_tree_fork_nodes", ctypes.c_int, [_P, _P, _U8P, _U8P, _U8P, ctypes.c_size_t, _U8P, _P, _P]),
     ("stl_shamap_tree_revert", ctypes.c_int, [_P]),
+    ("stl_shamap_tree_fetch_pack_device", ctypes.c_int, [_P, _P, _P, _P, _P]),
+    ("stl_shamap_tree_fetch_pack", ctypes.c_int, [_P, _P, _P, _P]),
 ]
 
 

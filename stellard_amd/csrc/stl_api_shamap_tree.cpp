@@ -1,11 +1,12 @@
 // stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
 // ledger's changes, the inner nodes an apply makes new, lookup by key, the
 // difference of two trees, the fork of one tree into another and the one-step
-// revert): the stl_shamap_tree_* entry points of include/stl.h;
-// kernels: stl_shamap_tree.hip, stl_shamap_lookup.hip, and the sort and level
-// kernels of stl_shamap.hip.
+// revert, the fetch pack against another tree): the stl_shamap_tree_* entry
+// points of include/stl.h; kernels: stl_shamap_tree.hip, stl_shamap_lookup.hip,
+// stl_shamap_fetch.hip, and the sort and level kernels of stl_shamap.hip.
 #include "stl_host.h"
 #include "stl_shamap.h"
+#include "stl_shamap_fetch.h"
 #include "stl_shamap_lookup.h"
 #include "stl_shamap_tree.h"
 #include "stl_shamap_tree_core.h"
@@ -292,6 +293,32 @@ int compare_enqueue(Device& d, const stl_shamap_tree* a, const stl_shamap_tree* 
                                           c->shamap.p, temp, fault_now, s));
   return STL_OK;
 }
+
+// ---- the fetch pack: read-only as the two above ----
+int check_fetch_args(const stl_shamap_tree* want, const stl_shamap_nodes_out* out, const void* d_counts,
+                     bool device_form) {
+  STL_RC(check_nodes_out(out, device_form));
+  if (!want) return STL_EINVAL;
+  if (device_form && ((uintptr_t)d_counts & 3u) != 0) return STL_EINVAL;
+  return STL_OK;
+}
+
+// want's pack against have (or none) on stream s (g_trees.mu held, the trees
+// live on d): enqueued, never waited for; the workspace is the stream context's.
+int fetch_enqueue(Device& d, const stl_shamap_tree* want, const stl_shamap_tree* have, const ShamapEmit& emit,
+                  uint32_t* d_counts, hipStream_t s) {
+  size_t temp = 0;
+  STL_TRY(stl::shamap_temp_bytes(stl::kTreeBuckets, &temp));
+  const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
+  std::lock_guard<std::mutex> lk(c->mu);
+  STL_RC(c->shamap.ensure(stl::shamap_fetch_workspace_bytes(want->bound, have ? have->bound : 0, temp)));
+  stl::TreeGen hg{};
+  if (have) hg = have->gen(have->live);
+  STL_TRY(stl::launch_shamap_tree_fetch_pack(want->gen(want->live), want->capacity, want->bound, have ? &hg : nullptr,
+                                             have ? have->capacity : 0, have ? have->bound : 0, emit, d_counts,
+                                             c->shamap.p, temp, fault_now, phase_clock(d), s));
+  return STL_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -518,6 +545,33 @@ int stl_shamap_tree_compare(stl_shamap_tree* a, stl_shamap_tree* b, const stl_sh
     call.download(out->leaf_a, d.msg, 32 * rows);
     call.download(out->leaf_b, d.wide, 32 * rows);
     return STL_OK;
+  });
+}
+
+int stl_shamap_tree_fetch_pack_device(stl_shamap_tree* want, stl_shamap_tree* have, const stl_shamap_nodes_out* out,
+                                      uint32_t* d_counts, void* stream) {
+  STL_RC(check_fetch_args(want, out, d_counts, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(trees_for_call(want, have ? have : want, &d));
+  return fetch_enqueue(*d, want, have, emit_of(*out), d_counts, static_cast<hipStream_t>(stream));
+}
+
+int stl_shamap_tree_fetch_pack(stl_shamap_tree* want, stl_shamap_tree* have, const stl_shamap_nodes_out* out,
+                               uint32_t counts[8]) {
+  STL_RC(check_fetch_args(want, out, counts, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(trees_for_call(want, have ? have : want, &dp));
+  HostCall call("stl_shamap_tree_fetch_pack", out->max_nodes, *dp);
+  return call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(d.status.ensure(32));
+    NodeStage stage;
+    STL_RC(stage.ensure(d, *out));
+    STL_RC(fetch_enqueue(d, want, have, stage.emit, static_cast<uint32_t*>(d.status.p), d.stream));
+    call.download(counts, d.status, 32);
+    return stage.fetch(call, *out);
   });
 }
 

@@ -81,6 +81,13 @@ hipError_t shamap_exclusive_scan(void* temp, size_t temp_bytes, const uint32_t* 
 hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
                                 uint32_t d_first, uint32_t d_last, bool (*fault)(), hipStream_t stream,
                                 const ShamapEmit* emit = nullptr);
+// The two halves of launch_shamap_levels on their own, for a caller that
+// interleaves the level launches of two arrays (stl_shamap_fetch.hip): the
+// neighbour kernel, once per array, and the plain level kernel for one depth.
+hipError_t launch_shamap_neighbours(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint32_t n, bool (*fault)(),
+                                    hipStream_t stream);
+hipError_t launch_shamap_level(uint32_t* hdr, const int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
+                               uint32_t d, bool (*fault)(), hipStream_t stream);
 
 }  // namespace stl
 

@@ -529,4 +529,18 @@ hipError_t launch_shamap_levels(uint32_t* hdr, int8_t* l, const uint8_t* skey, u
   return shamap_level_launches(hdr, l, skey, slot, lg, d_first, d_last, emit, fault, stream);
 }
 
+hipError_t launch_shamap_neighbours(uint32_t* hdr, int8_t* l, const uint8_t* skey, uint32_t n, bool (*fault)(),
+                                    hipStream_t stream) {
+  if (n == 0 || !hdr || !l || !skey) return hipErrorInvalidValue;
+  SM_LAUNCH(shamap_neighbour_kernel, grid_of(n), kSmBlock, skey, n, l, hdr);
+  return hipSuccess;
+}
+
+hipError_t launch_shamap_level(uint32_t* hdr, const int8_t* l, const uint8_t* skey, uint8_t* slot, uint32_t n,
+                               uint32_t d, bool (*fault)(), hipStream_t stream) {
+  if (n == 0 || !hdr || !l || !skey || !slot || d >= kShamapDepths) return hipErrorInvalidValue;
+  const uint32_t g = grid_of(n);
+  return shamap_level_launches(hdr, l, skey, slot, g < kSmLevelGrid ? g : kSmLevelGrid, d, d, nullptr, fault, stream);
+}
+
 }  // namespace stl

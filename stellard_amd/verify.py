@@ -1127,6 +1127,48 @@ class ShamapTree(_DeviceObject):
         N.check(N.load().stl_shamap_tree_compare(self._h, other._h, ctypes.byref(out)), "stl_shamap_tree_compare")
         return diff
 
+    # ---- SHAMap::getFetchPack: this tree's inner nodes that another tree does not hold ----
+    @staticmethod
+    def _have_handle(have):
+        if have is None:
+            return None
+        if not isinstance(have, ShamapTree):
+            raise ValueError("have must be a ShamapTree or None")
+        return have._h
+
+    def fetch_pack_device(self, have=None, max_nodes=None, nodes=None, ids=True, meta=True, counts=False,
+                          stream=None):
+        """stl_shamap_tree_fetch_pack_device: every inner node of this tree
+        (want) for which ``have`` holds no inner node at the same ID with the
+        same hash -> a ``DeviceNodes`` of ``max_nodes`` rows (made here, or the
+        one given as ``nodes``), or (nodes, int32[8] counts) with ``counts``
+        (True, or a tensor to write them to).  ``have`` None: every inner node
+        of this tree.  Both trees are only read.  The leaves of the pack are
+        ``compare_device(have)``'s A_ONLY and CHANGED rows.  Asynchronous on
+        ``stream``."""
+        hh = self._have_handle(have)
+        nodes = _device_nodes(nodes, max_nodes, ids, meta, "cuda")
+        cnt = _node_counts(counts, 8, nodes.count.device)
+        if cnt is not None and (not cnt.is_cuda or not cnt.is_contiguous()):
+            raise ValueError("device entry point needs contiguous CUDA tensors")
+        out = nodes.struct()
+        N.check(N.load().stl_shamap_tree_fetch_pack_device(
+            self._h, hh, ctypes.byref(out), ctypes.c_void_p(cnt.data_ptr()) if cnt is not None else None,
+            _stream_ptr(stream)), "stl_shamap_tree_fetch_pack_device")
+        return nodes if cnt is None else (nodes, cnt)
+
+    def fetch_pack(self, have=None, max_nodes=0, ids=True, meta=True):
+        """stl_shamap_tree_fetch_pack: host memory, synchronous -> (nodes,
+        [8 counts]): a ``HostNodes`` whose arrays hold min(count, max_nodes)
+        rows."""
+        hh = self._have_handle(have)
+        nodes = HostNodes(max_nodes, ids, meta)
+        cnt = np.zeros(8, dtype=np.uint32)
+        out = nodes.struct()
+        N.check(N.load().stl_shamap_tree_fetch_pack(self._h, hh, ctypes.byref(out), _buf(cnt)),
+                "stl_shamap_tree_fetch_pack")
+        return nodes, [int(x) for x in cnt]
+
 
 # ---- the difference of two resident trees (stl_shamap_tree_compare*) ----
 
