@@ -1232,6 +1232,83 @@ int stl_shamap_tree_fetch_pack_device(stl_shamap_tree *want, stl_shamap_tree *ha
 int stl_shamap_tree_fetch_pack(stl_shamap_tree *want, stl_shamap_tree *have, const stl_shamap_nodes_out *out,
                                uint32_t counts[8]);
 
+/* ---- resident SHAMap: SHAMap::getNodeFat and SHAMap::getPath by node ID ----
+ * A peer that acquires a ledger or a transaction set asks with TMGetLedger (liTX_NODE / liAS_NODE),
+ * and for every node ID of the packet the reference calls map->getNodeFat(id, nodeIDs, rawNodes,
+ * fatRoot, fatLeaves) (PeerImp.cpp:597-650, SHAMapSync.cpp:231-306): a walk by (depth, masked key),
+ * which a node store keyed by hash cannot make.  SHAMap::getPath / getTrustedPath
+ * (SHAMap.cpp:1079-1109) is the same question asked by key.  The call below answers n such requests,
+ * n <= STL_SHAMAP_GET_MAX_REQUESTS, from a stl_shamap_tree where it lies.
+ * REQUESTS: d_id n * 32 bytes, 16-byte aligned; d_depth n bytes; d_mode n bytes or NULL (every
+ * request STL_SHAMAP_GET_FAT).  NODE: the node at (depth, id) alone -- getNodeFat of the root with
+ * fatRoot false, and hasNode.  FAT: what getNodeFat emits with fatRoot true.  PATH: getPath(id); id
+ * is a full key and depth is not read.
+ * THE NODE AT (depth, id): with [lo, hi) the tree's keys whose first `depth` nibbles are id's and
+ * c = hi - lo, it is an inner node when c >= 2 or depth == 0 && c == 1; a leaf when c == 1,
+ * depth >= 1 and (depth == 1 or the range one nibble shorter holds two keys or more); the empty root
+ * when depth == 0 && c == 0; else absent.  An id with a bit set past its first `depth` nibbles is
+ * absent: the wire constructor does not mask, and the reference's nodeID != wanted then fails.
+ * ANSWERS, n entries each: d_status (bytes) STL_SHAMAP_AT_*; d_first and d_rows (words): the
+ * request's node rows are [first, first + rows), first the exclusive prefix sum of rows in request
+ * order; d_leaf_key and d_leaf_hash (n * 32 bytes, 16-byte aligned, or NULL): for AT_LEAF and
+ * AT_OTHER_LEAF the leaf's key and leaf hash, zeros otherwise.
+ * ROWS go into `out` as the node-storing calls fill it (hash, 512-byte body, optional id, optional
+ * meta with depth and leaf mask), here in a fixed order.  A leaf has no row.  NODE on an inner node:
+ * one row.  FAT on an inner node: with L the leading nibbles the range's first and last key share
+ * (depth <= L <= 63), the inner nodes along id at depths depth .. L -- the chain of nodes with a
+ * single, inner branch that the reference's do-while follows -- and then the inner children of the
+ * node at L in branch order; leaf children are no rows, the node's leaf mask and body name them
+ * (fatLeaves) and the caller's node store holds the blobs; the root of a one-key tree is one row.
+ * PATH: the inner nodes along the key at depths 0 .. D - 1 in depth order (getPath's vector order,
+ * getTrustedPath's reversed), D the first depth at which fewer than two keys share the key's prefix
+ * and at least 1 in a tree that holds a key; what sits at depth D is AT_LEAF (the key), AT_OTHER_LEAF
+ * (another key: its key is given, the proof of absence) or AT_ABSENT (an empty branch), and the rows
+ * are written in all three cases.  An empty tree: no row, AT_ABSENT.  No request has more than 80
+ * rows.  Requests are answered independently: a node two requests want is stored once for each.
+ * *out->count is the sum of rows whatever max_nodes is; nothing is stored at an index >= max_nodes.
+ * d_counts (8 words, or NULL): [0] the sum of rows, [1] requests AT_INNER, [2] AT_LEAF or
+ * AT_OTHER_LEAF, [3] every other status, [4] buckets gathered, [5] items gathered, [6] distinct
+ * nodes among the rows stored, [7] items of the tree.
+ * READ-ONLY: content, count, root, host bound, revert state and work areas of the tree are unchanged
+ * whatever the call returns; everything written besides the caller's arrays is the stream
+ * context's.  It may run beside lookups, compares, fetch packs and other such calls on any streams;
+ * against an apply or a fork into the tree the caller orders it.
+ * The device form is asynchronous on `stream` and never waits on the host.  The cost follows the
+ * requests: only the buckets that hold a wanted node at depth >= 4 are gathered and hashed level by
+ * level, and the 4,369 prefixes above the buckets are folded once.  The 60 level launches run
+ * whatever the requests are: one request costs what the launches cost.  The host form takes arrays
+ * of any alignment, stages through the device's buffers, waits once for the count and copies back
+ * min(count, max_nodes) rows.
+ * FAILURE: *out->count and d_counts are written by the call's last launch alone; the per-request
+ * arrays and the rows may be partly written by a call that fails.
+ * Before any device work: what the node-storing calls refuse in `out`; a NULL tree; a handle that
+ * is not live; a tree of another device than the calling thread's; with n > 0 a NULL d_id, d_depth,
+ * d_status, d_first or d_rows; d_id, d_leaf_key or d_leaf_hash not 16-byte aligned, d_first, d_rows
+ * or d_counts not 4-byte aligned; n > STL_SHAMAP_GET_MAX_REQUESTS is STL_EINVAL.  n == 0 is STL_OK:
+ * *count = 0 and zero counts, nothing else.
+ * MEMORY: in the stream context 73 B per item of the tree's host bound, 5 B per task
+ * (min(80 n, max_nodes)), 1 MiB of per-bucket words, the 4,369 top values and the scans' temporary
+ * storage.  Nothing is sized by the tree's node count.
+ * With stl_set_phase_timing on the call adds to stl_stats.phase_ns[0..2]: ranges, tasks and gather;
+ * the levels; top and finish. */
+#define STL_SHAMAP_GET_MAX_REQUESTS 16777216u
+#define STL_SHAMAP_GET_NODE 0u
+#define STL_SHAMAP_GET_FAT 1u
+#define STL_SHAMAP_GET_PATH 2u
+#define STL_SHAMAP_AT_ABSENT 0u     /* "Peer requested node not in map"; PATH: an empty branch */
+#define STL_SHAMAP_AT_INNER 1u
+#define STL_SHAMAP_AT_LEAF 2u
+#define STL_SHAMAP_AT_EMPTY_ROOT 3u /* the root of an empty tree: getNodeFat returns false */
+#define STL_SHAMAP_AT_INVALID 4u    /* depth > 63 (SHAMapNodeID::isValid), or an unknown mode */
+#define STL_SHAMAP_AT_OTHER_LEAF 5u /* PATH only: the path ends at a leaf with another key */
+int stl_shamap_tree_get_nodes_device(stl_shamap_tree *t, const uint8_t *d_id, const uint8_t *d_depth,
+                                     const uint8_t *d_mode, size_t n, uint8_t *d_status, uint32_t *d_first,
+                                     uint32_t *d_rows, uint8_t *d_leaf_key, uint8_t *d_leaf_hash,
+                                     const stl_shamap_nodes_out *out, uint32_t *d_counts, void *stream);
+int stl_shamap_tree_get_nodes(stl_shamap_tree *t, const uint8_t *id, const uint8_t *depth, const uint8_t *mode,
+                              size_t n, uint8_t *status, uint32_t *first, uint32_t *rows, uint8_t *leaf_key,
+                              uint8_t *leaf_hash, const stl_shamap_nodes_out *out, uint32_t counts[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,18 @@ STL_SHAMAP_DIFF_A_ONLY = 1
 STL_SHAMAP_DIFF_B_ONLY = 2
 STL_SHAMAP_DIFF_CHANGED = 3
 
+# resident SHAMap nodes by node ID and paths by key (stl_shamap_tree_get_nodes*)
+STL_SHAMAP_GET_MAX_REQUESTS = 16777216
+STL_SHAMAP_GET_NODE = 0
+STL_SHAMAP_GET_FAT = 1
+STL_SHAMAP_GET_PATH = 2
+STL_SHAMAP_AT_ABSENT = 0
+STL_SHAMAP_AT_INNER = 1
+STL_SHAMAP_AT_LEAF = 2
+STL_SHAMAP_AT_EMPTY_ROOT = 3
+STL_SHAMAP_AT_INVALID = 4
+STL_SHAMAP_AT_OTHER_LEAF = 5
+
 # arithmetic self-test (stl_debug_selftest_*; row formats in csrc/stl_selftest.h)
 STL_SELFTEST_OPS = 47
 STL_SELFTEST_GROUP_OPS = 7
@@ -229,6 +241,9 @@ SYMBOLS = [
     ("stl_shamap_tree_revert", ctypes.c_int, [_P]),
     ("stl_shamap_tree_fetch_pack_device", ctypes.c_int, [_P, _P, _P, _P, _P]),
     ("stl_shamap_tree_fetch_pack", ctypes.c_int, [_P, _P, _P, _P]),
+    ("stl_shamap_tree_get_nodes_device", ctypes.c_int,
+     [_P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("stl_shamap_tree_get_nodes", ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 

@@ -28,6 +28,9 @@
   tests/native/libhostemu_shamap_fetch.so  the fetch pack's bucket, hasInnerNode
                                  and top rules and the staged call between
                                  generations of their trees' capacities
+  tests/native/libhostemu_shamap_get.so  the rules of the answers by node ID
+                                 (range, kind, FAT and PATH rows) and the
+                                 staged call over a generation of its tree's size
   oracle/build/liboracle.so      test oracle: CPU restatement (make)
   oracle/_ref/libsodium_ref.so   test oracle: reference call path over libsodium
 
@@ -46,7 +49,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 PRODUCT_SRCS = ["stl_kernels.hip", "stl_keyset.hip", "stl_signer.hip", "stl_acctdir.hip", "stl_sigcache.hip",
                 "stl_shamap.hip", "stl_shamap_tree.hip", "stl_shamap_lookup.hip", "stl_shamap_fetch.hip",
-                "stl_selftest.hip",
+                "stl_shamap_get.hip", "stl_selftest.hip",
                 "stl_api.cpp", "stl_api_keyset.cpp", "stl_api_authority.cpp", "stl_api_sigcache.cpp",
                 "stl_api_shamap.cpp", "stl_api_shamap_tree.cpp", "stl_batcher.cpp"]
 PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe25519.h", "stl_ge25519.h",
@@ -59,6 +62,7 @@ PRODUCT_DEPS = PRODUCT_SRCS + ["stl_kernels.h", "stl_verify_core.h", "stl_fe2551
                                "stl_shamap_tree_core.h", "stl_shamap_tree.h",
                                "stl_shamap_lookup_core.h", "stl_shamap_lookup.h",
                                "stl_shamap_fetch_core.h", "stl_shamap_fetch.h",
+                               "stl_shamap_get_core.h", "stl_shamap_get.h",
                                "stl_group.h", "stl_selftest.h", "stl_host.h",
                                os.path.join("..", "..", "include", "stl.h")]
 
@@ -94,7 +98,7 @@ def _run(cmd, cwd=ROOT):
 HOST_ONLY = ["stl_host.h"]
 HOST_DEPS = HOST_ONLY + ["stl_kernels.h", "stl_keyset.h", "stl_keyset_map.h", "stl_keycache.h", "stl_signer.h",
              "stl_acctdir.h", "stl_acctdir_core.h", "stl_sigcache.h", "stl_sigcache_core.h", "stl_shamap.h",
-             "stl_shamap_tree.h", "stl_shamap_tree_core.h", "stl_shamap_lookup.h", "stl_shamap_fetch.h", "stl_shamap_core.h", "stl_sha512.h", os.path.join("..", "..", "include", "stl.h")]
+             "stl_shamap_tree.h", "stl_shamap_tree_core.h", "stl_shamap_lookup.h", "stl_shamap_fetch.h", "stl_shamap_get.h", "stl_shamap_core.h", "stl_sha512.h", os.path.join("..", "..", "include", "stl.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 
 
@@ -170,6 +174,9 @@ SMALL_HARNESSES = {
     "shamap_fetch": ("hostemu_shamap_fetch.cpp", ("stl_shamap_fetch_core.h", "stl_shamap_lookup_core.h",
                                                   "stl_shamap_tree_core.h", "stl_shamap_core.h", "stl_sha512.h",
                                                   "stl_fe25519.h")),
+    "shamap_get": ("hostemu_shamap_get.cpp", ("stl_shamap_get_core.h", "stl_shamap_fetch_core.h",
+                                              "stl_shamap_lookup_core.h", "stl_shamap_tree_core.h",
+                                              "stl_shamap_core.h", "stl_sha512.h", "stl_fe25519.h")),
 }
 _small_lock = threading.Lock()
 
@@ -239,6 +246,10 @@ def build_hostemu_shamap_fetch(force=False):
     return _build_small("shamap_fetch", force)
 
 
+def build_hostemu_shamap_get(force=False):
+    return _build_small("shamap_get", force)
+
+
 def build_oracle():
     oracle = os.path.join(ROOT, "oracle")
     targets = ["build/liboracle.so"]
@@ -264,7 +275,8 @@ def main(argv=None):
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
                 ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force),
                 ex.submit(build_hostemu_shamap_nodes, force), ex.submit(build_hostemu_shamap_lookup, force),
-                ex.submit(build_hostemu_shamap_fork, force), ex.submit(build_hostemu_shamap_fetch, force)]
+                ex.submit(build_hostemu_shamap_fork, force), ex.submit(build_hostemu_shamap_fetch, force),
+                ex.submit(build_hostemu_shamap_get, force)]
         for j in jobs:
             j.result()
     build_oracle()

@@ -1,12 +1,14 @@
 // stl_api_shamap_tree.cpp -- the resident SHAMap (a state tree's root from each
 // ledger's changes, the inner nodes an apply makes new, lookup by key, the
 // difference of two trees, the fork of one tree into another and the one-step
-// revert, the fetch pack against another tree): the stl_shamap_tree_* entry
-// points of include/stl.h; kernels: stl_shamap_tree.hip, stl_shamap_lookup.hip,
-// stl_shamap_fetch.hip, and the sort and level kernels of stl_shamap.hip.
+// revert, the fetch pack against another tree, nodes by node ID and paths by
+// key): the stl_shamap_tree_* entry points of include/stl.h; kernels:
+// stl_shamap_tree.hip, stl_shamap_lookup.hip, stl_shamap_fetch.hip,
+// stl_shamap_get.hip, and the sort and level kernels of stl_shamap.hip.
 #include "stl_host.h"
 #include "stl_shamap.h"
 #include "stl_shamap_fetch.h"
+#include "stl_shamap_get.h"
 #include "stl_shamap_lookup.h"
 #include "stl_shamap_tree.h"
 #include "stl_shamap_tree_core.h"
@@ -319,6 +321,41 @@ int fetch_enqueue(Device& d, const stl_shamap_tree* want, const stl_shamap_tree*
                                              c->shamap.p, temp, fault_now, phase_clock(d), s));
   return STL_OK;
 }
+
+// ---- nodes by node ID, paths by key: read-only as the three above ----
+int check_get_args(const stl_shamap_tree* t, const uint8_t* id, const uint8_t* depth, size_t n, const uint8_t* status,
+                   const uint32_t* first, const uint32_t* rows, const uint8_t* leaf_key, const uint8_t* leaf_hash,
+                   const stl_shamap_nodes_out* out, const void* counts, bool device_form) {
+  STL_RC(check_nodes_out(out, device_form));
+  if (!t || n > STL_SHAMAP_GET_MAX_REQUESTS) return STL_EINVAL;
+  if (n && (!id || !depth || !status || !first || !rows)) return STL_EINVAL;
+  if (!device_form) return STL_OK;  // host arrays: any alignment serves
+  if ((((uintptr_t)id | (uintptr_t)leaf_key | (uintptr_t)leaf_hash) & 15u) != 0) return STL_EINVAL;
+  if ((((uintptr_t)first | (uintptr_t)rows | (uintptr_t)counts) & 3u) != 0) return STL_EINVAL;
+  return STL_OK;
+}
+
+// No request: a count of zero and zero counts, nothing else.
+int get_nothing(uint32_t* d_count, uint32_t* d_counts, hipStream_t s) {
+  STL_TRY(hipMemsetAsync(d_count, 0, 4, s));
+  if (d_counts) STL_TRY(hipMemsetAsync(d_counts, 0, 32, s));
+  return STL_OK;
+}
+
+// n >= 1 requests against t's live generation on stream s (g_trees.mu held, t
+// live on d): enqueued, never waited for; the workspace is the stream context's.
+int get_enqueue(Device& d, const stl_shamap_tree* t, const stl::ShamapGet& rq, size_t n, const ShamapEmit& emit,
+                uint32_t* d_counts, hipStream_t s) {
+  size_t temp = 0;
+  STL_TRY(stl::shamap_temp_bytes(n > stl::kTreeBuckets ? n : stl::kTreeBuckets, &temp));
+  const std::shared_ptr<StreamCtx> c = stream_ctx(d, s);
+  std::lock_guard<std::mutex> lk(c->mu);
+  STL_RC(c->shamap.ensure(
+      stl::shamap_get_workspace_bytes(t->bound, stl::shamap_get_task_rows(n, emit.max_nodes), temp)));
+  STL_TRY(stl::launch_shamap_tree_get_nodes(t->gen(t->live), t->capacity, t->bound, rq, (uint32_t)n, emit, d_counts,
+                                            c->shamap.p, temp, fault_now, phase_clock(d), s));
+  return STL_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -572,6 +609,69 @@ int stl_shamap_tree_fetch_pack(stl_shamap_tree* want, stl_shamap_tree* have, con
     STL_RC(fetch_enqueue(d, want, have, stage.emit, static_cast<uint32_t*>(d.status.p), d.stream));
     call.download(counts, d.status, 32);
     return stage.fetch(call, *out);
+  });
+}
+
+int stl_shamap_tree_get_nodes_device(stl_shamap_tree* t, const uint8_t* d_id, const uint8_t* d_depth,
+                                     const uint8_t* d_mode, size_t n, uint8_t* d_status, uint32_t* d_first,
+                                     uint32_t* d_rows, uint8_t* d_leaf_key, uint8_t* d_leaf_hash,
+                                     const stl_shamap_nodes_out* out, uint32_t* d_counts, void* stream) {
+  STL_RC(check_get_args(t, d_id, d_depth, n, d_status, d_first, d_rows, d_leaf_key, d_leaf_hash, out, d_counts, true));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* d = nullptr;
+  STL_RC(g_trees.for_call(t, &d));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) return get_nothing(out->count, d_counts, s);
+  const stl::ShamapGet rq{d_id, d_depth, d_mode, d_status, d_first, d_rows, d_leaf_key, d_leaf_hash};
+  return get_enqueue(*d, t, rq, n, emit_of(*out), d_counts, s);
+}
+
+int stl_shamap_tree_get_nodes(stl_shamap_tree* t, const uint8_t* id, const uint8_t* depth, const uint8_t* mode,
+                              size_t n, uint8_t* status, uint32_t* first, uint32_t* rows, uint8_t* leaf_key,
+                              uint8_t* leaf_hash, const stl_shamap_nodes_out* out, uint32_t counts[8]) {
+  STL_RC(check_get_args(t, id, depth, n, status, first, rows, leaf_key, leaf_hash, out, counts, false));
+  std::lock_guard<std::mutex> lk(g_trees.mu);
+  Device* dp = nullptr;
+  STL_RC(g_trees.for_call(t, &dp));
+  HostCall call("stl_shamap_tree_get_nodes", n, *dp);
+  return call.run([&]() -> int {
+    Device& d = call.d;
+    STL_RC(d.status.ensure(32));
+    NodeStage stage;
+    STL_RC(stage.ensure(d, *out));
+    uint32_t* const d_counts = static_cast<uint32_t*>(d.status.p);
+    if (n == 0) {
+      STL_RC(get_nothing(stage.emit.count, d_counts, d.stream));
+    } else {
+      // the depth bytes, and behind them the mode bytes
+      const size_t mode_at = align256(n);
+      STL_RC(d.sig.ensure(mode_at + n));
+      STL_RC(call.upload(d.pk, id, n * 32));
+      STL_RC(call.upload(d.sig, depth, n));
+      uint8_t* const d_mode = static_cast<uint8_t*>(d.sig.p) + mode_at;
+      if (mode) STL_TRY(hipMemcpyAsync(d_mode, mode, n, hipMemcpyHostToDevice, d.stream));
+      STL_RC(d.bitmap.ensure(n));
+      STL_RC(d.txid.ensure(4 * n));
+      STL_RC(d.gather.ensure(4 * n));
+      if (leaf_key) STL_RC(d.msg.ensure(32 * n));
+      if (leaf_hash) STL_RC(d.wide.ensure(32 * n));
+      const stl::ShamapGet rq{static_cast<const uint8_t*>(d.pk.p),
+                              static_cast<const uint8_t*>(d.sig.p),
+                              mode ? d_mode : nullptr,
+                              static_cast<uint8_t*>(d.bitmap.p),
+                              static_cast<uint32_t*>(d.txid.p),
+                              static_cast<uint32_t*>(d.gather.p),
+                              leaf_key ? static_cast<uint8_t*>(d.msg.p) : nullptr,
+                              leaf_hash ? static_cast<uint8_t*>(d.wide.p) : nullptr};
+      STL_RC(get_enqueue(d, t, rq, n, stage.emit, d_counts, d.stream));
+      call.download(status, d.bitmap, n);
+      call.download(first, d.txid, 4 * n);
+      call.download(rows, d.gather, 4 * n);
+      call.download(leaf_key, d.msg, 32 * n);
+      call.download(leaf_hash, d.wide, 32 * n);
+    }
+    call.download(counts, d.status, 32);
+    return stage.fetch(call, *out);  // the one wait of its own: how many rows to bring back
   });
 }
 

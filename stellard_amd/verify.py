@@ -1169,6 +1169,102 @@ class ShamapTree(_DeviceObject):
                 "stl_shamap_tree_fetch_pack")
         return nodes, [int(x) for x in cnt]
 
+    # ---- SHAMap::getNodeFat / getPath: nodes by node ID, paths by key ----
+    def get_nodes_device(self, ids, depths, modes=None, max_nodes=None, nodes=None, node_ids=True, meta=True,
+                         leaves=True, counts=False, stream=None):
+        """stl_shamap_tree_get_nodes_device: n requests (ids (n, 32) uint8,
+        depths uint8[n], modes uint8[n] of SHAMAP_GET_* or None: every request
+        FAT) -> a ``GetAnswer``: status uint8[n] (SHAMAP_AT_*), first / rows
+        int32[n] (request i's rows are nodes rows first[i] .. first[i] +
+        rows[i]), leaf_key / leaf_hash (n, 32) uint8 or None (``leaves``
+        False), nodes (a ``DeviceNodes`` of ``max_nodes`` rows, made here, or
+        the one given), counts int32[8] or None.  The tree is only read.
+        Asynchronous on ``stream``."""
+        import torch
+        if ids is None or ids.dim() != 2:
+            raise ValueError("ids must be (n, 32) bytes")
+        n = ids.shape[0]
+        _check_hashes(n, ids=ids)
+        if n > SHAMAP_GET_MAX_REQUESTS:
+            raise ValueError("more than SHAMAP_GET_MAX_REQUESTS requests")
+        for name, t in (("depths", depths), ("modes", modes)):
+            if t is None and name == "modes":
+                continue
+            if t is None or t.dtype != torch.uint8 or tuple(t.shape) != (n,):
+                raise ValueError(f"{name} must be uint8[n]")
+        nodes = _device_nodes(nodes, max_nodes, node_ids, meta, "cuda")
+        dev = nodes.count.device
+        cnt = _node_counts(counts, 8, dev)
+        rows = max(n, 1)  # a place to point at even for no request
+        a = GetAnswer()
+        a.n, a.nodes, a.counts = n, nodes, cnt
+        a.status = torch.empty(rows, dtype=torch.uint8, device=dev)
+        a.first = torch.empty(rows, dtype=torch.int32, device=dev)
+        a.rows = torch.empty(rows, dtype=torch.int32, device=dev)
+        a.leaf_key = torch.empty((rows, 32), dtype=torch.uint8, device=dev) if leaves else None
+        a.leaf_hash = torch.empty((rows, 32), dtype=torch.uint8, device=dev) if leaves else None
+        for t in (ids, depths, modes, cnt):
+            if t is not None and (not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("device entry point needs contiguous CUDA tensors")
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        out = nodes.struct()
+        N.check(N.load().stl_shamap_tree_get_nodes_device(
+            self._h, p(ids), p(depths), p(modes), n, p(a.status), p(a.first), p(a.rows), p(a.leaf_key),
+            p(a.leaf_hash), ctypes.byref(out), p(cnt), _stream_ptr(stream)), "stl_shamap_tree_get_nodes_device")
+        return a
+
+    def get_nodes(self, ids, depths, modes=None, max_nodes=0, node_ids=True, meta=True, leaves=True):
+        """stl_shamap_tree_get_nodes: host memory, synchronous.  ids (n, 32)
+        uint8, depths uint8[n], modes uint8[n] or None -> a ``GetAnswer`` of
+        numpy arrays: nodes a ``HostNodes`` whose arrays hold min(count,
+        max_nodes) rows, counts a list of 8 ints."""
+        ids = np.ascontiguousarray(ids)
+        if ids.dtype != np.uint8 or ids.ndim != 2 or ids.shape[1] != 32:
+            raise ValueError("ids must be (n, 32) uint8")
+        n = ids.shape[0]
+        if n > SHAMAP_GET_MAX_REQUESTS:
+            raise ValueError("more than SHAMAP_GET_MAX_REQUESTS requests")
+        depths = np.ascontiguousarray(depths)
+        if depths.dtype != np.uint8 or depths.shape != (n,):
+            raise ValueError("depths must be uint8[n]")
+        if modes is not None:
+            modes = np.ascontiguousarray(modes)
+            if modes.dtype != np.uint8 or modes.shape != (n,):
+                raise ValueError("modes must be uint8[n]")
+        a = GetAnswer()
+        a.n, a.nodes = n, HostNodes(max_nodes, node_ids, meta)
+        rows = max(n, 1)
+        a.status = np.zeros(rows, np.uint8)
+        a.first, a.rows = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32)
+        a.leaf_key = np.zeros((rows, 32), np.uint8) if leaves else None
+        a.leaf_hash = np.zeros((rows, 32), np.uint8) if leaves else None
+        cnt = np.zeros(8, dtype=np.uint32)
+        out = a.nodes.struct()
+        b = lambda x: _buf(x) if x is not None and n else None  # noqa: E731
+        N.check(N.load().stl_shamap_tree_get_nodes(
+            self._h, b(ids), b(depths), b(modes), n, _buf(a.status), _buf(a.first), _buf(a.rows),
+            _buf(a.leaf_key) if leaves else None, _buf(a.leaf_hash) if leaves else None, ctypes.byref(out),
+            _buf(cnt)), "stl_shamap_tree_get_nodes")
+        a.counts = [int(x) for x in cnt]
+        return a
+
+
+SHAMAP_GET_MAX_REQUESTS = N.STL_SHAMAP_GET_MAX_REQUESTS
+SHAMAP_GET_NODE, SHAMAP_GET_FAT, SHAMAP_GET_PATH = N.STL_SHAMAP_GET_NODE, N.STL_SHAMAP_GET_FAT, N.STL_SHAMAP_GET_PATH
+SHAMAP_AT_ABSENT, SHAMAP_AT_INNER, SHAMAP_AT_LEAF = N.STL_SHAMAP_AT_ABSENT, N.STL_SHAMAP_AT_INNER, N.STL_SHAMAP_AT_LEAF
+SHAMAP_AT_EMPTY_ROOT, SHAMAP_AT_INVALID = N.STL_SHAMAP_AT_EMPTY_ROOT, N.STL_SHAMAP_AT_INVALID
+SHAMAP_AT_OTHER_LEAF = N.STL_SHAMAP_AT_OTHER_LEAF
+
+
+class GetAnswer:
+    """What ``ShamapTree.get_nodes[_device]`` returns: n, status, first, rows,
+    leaf_key, leaf_hash, nodes (DeviceNodes / HostNodes) and counts; the first
+    ``n`` entries of the per-request arrays are the answers."""
+
+    def request_rows(self, i):
+        """(first, rows) of request i as ints (waits for the device)."""
+        return int(self.first[i]), int(self.rows[i])
+
 
 # ---- the difference of two resident trees (stl_shamap_tree_compare*) ----
 
