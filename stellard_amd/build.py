@@ -7,6 +7,8 @@
   tests/native/libhostemu_keyset_map.so  the keyset's key -> index map
   tests/native/libhostemu_keycache.so  the decoded-key cache's check, hash and
                                  victim choice, and the workspace layout
+  tests/native/libhostemu_keycache_alt.so  the cache's second-choice set and
+                                 insert rule, and phase 1's split point half
   tests/native/libhostemu_signer.so  Hash160 and the signer kernel's per-row
                                  function
   tests/native/libhostemu_acctdir.so  the account directory's hash, probe,
@@ -157,6 +159,9 @@ def build_hostemu_keyset(force=False):
 SMALL_HARNESSES = {
     "keyset_map": ("hostemu_keyset_map.cpp", ("stl_keyset_map.h",)),
     "keycache": ("hostemu_keycache.cpp", ("stl_keycache.h", "stl_fe25519.h", "stl_ge25519.h", "stl_kernels.h")),
+    "keycache_alt": ("hostemu_keycache_alt.cpp", ("stl_keycache.h", "stl_verify_core.h", "stl_fe25519.h",
+                                                  "stl_ge25519.h", "stl_sc25519.h", "stl_lattice.h", "stl_sha512.h",
+                                                  "stl_base_table.h")),
     "signer": ("hostemu_signer.cpp", ("stl_hash160.h", "stl_signer_core.h", "stl_txblob.h", "stl_sha512.h",
                                       "stl_fe25519.h")),
     "acctdir": ("hostemu_acctdir.cpp", ("stl_acctdir_core.h", "stl_hash160.h", "stl_signer_core.h", "stl_txblob.h",
@@ -208,6 +213,10 @@ def build_hostemu_keyset_map(force=False):
 
 def build_hostemu_keycache(force=False):
     return _build_small("keycache", force)
+
+
+def build_hostemu_keycache_alt(force=False):
+    return _build_small("keycache_alt", force)
 
 
 def build_hostemu_signer(force=False):
@@ -271,7 +280,8 @@ def main(argv=None):
     with ThreadPoolExecutor(max_workers=8) as ex:
         jobs = [ex.submit(build_product, force), ex.submit(build_hostemu, force),
                 ex.submit(build_hostemu_keyset, force), ex.submit(build_hostemu_keyset_map, force),
-                ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_signer, force),
+                ex.submit(build_hostemu_keycache, force), ex.submit(build_hostemu_keycache_alt, force),
+                ex.submit(build_hostemu_signer, force),
                 ex.submit(build_hostemu_acctdir, force), ex.submit(build_hostemu_sigcache, force),
                 ex.submit(build_hostemu_shamap, force), ex.submit(build_hostemu_shamap_tree, force),
                 ex.submit(build_hostemu_shamap_nodes, force), ex.submit(build_hostemu_shamap_lookup, force),

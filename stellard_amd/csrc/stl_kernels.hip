@@ -207,14 +207,73 @@ __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_point_k
 // and the chunk pays one kernel boundary instead of two -- the scalar
 // kernel alone ends in a ragged last round (3.2 rounds of 5 workgroups per
 // CU for 2^20 signatures).
-// A_READY: the key-cache kernels below ran first and left -A's x (words 20-28
-// of the row's state) and its decoding's verdict (word 29): the lane takes y
-// from the key bytes and decodes only R.
-constexpr int kKeyReadyQuad = 5;  // quads 5-7 = words 20-31 of the HalfState
-template <bool PRE_K, bool A_READY>
+// A_CACHED (the decoded-key cache, stl_keycache.h): the lane decodes only R
+// (verify_phase1_points_r) and then looks its key up itself -- the tags of the
+// key's primary set, the alternate set's only where those hold no match, the
+// matching way's x, key_cache_certify.  The gather comes after R's chain, so
+// nothing of it is live across the chain; the kernel's other waves (4 per
+// SIMD, issue-bound on the chain) cover its latency.  On a hit the lane
+// finishes the state with y from the key bytes and the certified x.  On a miss
+// it leaves the scalar half's `tops` in place, stores -Q raw (P2) and the R
+// half's flag in `pad` (kMissPointOk), and appends its row to the chunk's miss
+// list, one atomic per wave: key_cache_fill_kernel below decodes A and
+// finishes those rows, so A's chain is paid by the missed rows alone.  The
+// wave's fallback word holds the hit lanes' flags; the fill kernel ORs the
+// missed rows' in.
+
+// The set's tags (words 0-11 of the set: three quads) against the key's tag:
+// bit w = way w holds it.
+__device__ __forceinline__ uint32_t tag_matches(const uint4 t[3], const uint32_t tag[2]) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    m |= (t[i].x == tag[0] && t[i].y == tag[1]) ? 1u << (2 * i) : 0u;
+    m |= (t[i].z == tag[0] && t[i].w == tag[1]) ? 2u << (2 * i) : 0u;
+  }
+  return m;
+}
+static_assert(kKeyCacheWays == 6 && kKeyCacheTagWord == 0 && kKeyCacheXWord == 16, "tag_matches and the kernels below");
+
+// The lookup: X = the certified x(-A) of key A, or false (X is then zero or
+// an x that failed the check).  `look` is false for a lane that may not hit
+// (past the chunk's end).  Every lane of the wave calls it.
+__device__ __forceinline__ bool key_cache_lookup(fe& X, const uint32_t A[8], const uint4* cache, uint32_t mask,
+                                                 bool look) {
+  fe_0(X);
+  const uint4* set = cache + (size_t)key_cache_set(key_hash(A), mask) * (kKeyCacheSetBytes / 16);
+  uint32_t tag[2];
+  key_cache_tag(tag, A);
+  uint32_t match;
+  {
+    const uint4 tq[3] = {set[0], set[1], set[2]};
+    match = tag_matches(tq, tag);
+  }
+  if (match == 0) {  // the second-choice set, for these lanes only
+    const uint4* alt = cache + (size_t)key_cache_alt_set(A, mask) * (kKeyCacheSetBytes / 16);
+    const uint4 tq[3] = {alt[0], alt[1], alt[2]};
+    match = tag_matches(tq, tag);
+    set = alt;
+  }
+  const int way = match ? __ffs((int)match) - 1 : -1;  // the lowest way with the key's tag
+  bool hit = false;
+  if (__ballot(way >= 0) != 0) {  // a cold wave skips the check
+    uint32_t xb[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (way >= 0) {
+      const uint4 a = set[kKeyCacheXWord / 4 + 2 * way], b = set[kKeyCacheXWord / 4 + 2 * way + 1];
+      xb[0] = a.x; xb[1] = a.y; xb[2] = a.z; xb[3] = a.w;
+      xb[4] = b.x; xb[5] = b.y; xb[6] = b.z; xb[7] = b.w;
+    }
+    hit = key_cache_certify(X, A, xb) && way >= 0 && look;
+  }
+  return hit;
+}
+
+constexpr uint32_t kMissPointOk = 1u;  // HalfState::pad of a missed row between prep and fill
+template <bool PRE_K, bool A_CACHED>
 __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_prep_kernel(
     const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msg_or_k, const uint8_t* __restrict__ pk,
-    uint32_t base, uint32_t cnt, uint32_t policy, uint4* __restrict__ pre, uint64_t* __restrict__ fb_words) {
+    uint32_t base, uint32_t cnt, uint32_t policy, uint4* __restrict__ pre, uint64_t* __restrict__ fb_words,
+    const uint4* cache, uint32_t mask, uint32_t* __restrict__ miss, uint32_t* __restrict__ miss_ctr) {
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
   const bool live = t < cnt;
   const uint32_t tt = live ? t : cnt - 1;
@@ -239,31 +298,44 @@ __global__ __launch_bounds__(kBlock, STL_PRE_WAVES_PER_SIMD) void verify_prep_ke
         st_state(q + i, make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]));
     }
   }
-  if (A_READY) {
-    uint32_t kw[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const uint4 v = ld_state(q + kKeyReadyQuad + i);
-      kw[4 * i] = v.x; kw[4 * i + 1] = v.y; kw[4 * i + 2] = v.z; kw[4 * i + 3] = v.w;
-    }
-    fe nAx, nAy;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) nAx.v[i] = kw[i];
+  bool hit = true;  // the state below is final
+  if (A_CACHED) {
+    fe nQx, nQy, nAx, nAy;
+    const bool okr = verify_phase1_points_r(nQx, nQy, R, S, A, core_policy(policy));
+    hit = key_cache_lookup(nAx, A, cache, mask, live);
     fe_frombytes(nAy, A);
-    verify_phase1_points_keyed(h, R, S, A, core_policy(policy), nAx, nAy, kw[9] != 0);
+    finish_phase1_points(h, nAx, nAy, nQx, nQy, okr && hit);
+    if (!hit) {  // for the fill kernel: -Q as decoded, the R half's flag
+      h.P2x = nQx;
+      h.pad = okr ? kMissPointOk : 0u;
+    }
   } else {
     verify_phase1_points(h, R, S, A, core_policy(policy));
   }
   if ((policy & kModeFullLength) && (h.tops & kHalfOk)) h.tops |= kHalfFallback;
   if (live) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&h);
-    st_state(q + kHalfTopsWord / 4, make_uint4(w[8], w[9], w[10], w[11]));
+    if (hit)
+      st_state(q + kHalfTopsWord / 4, make_uint4(w[8], w[9], w[10], w[11]));
+    else
+      reinterpret_cast<uint32_t*>(q + 4)[3] = w[19];  // pad; `tops` stays the scalar half's
 #pragma unroll
     for (int i = kHalfScalarQuads; i < 14; ++i)
       st_state(q + i, make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]));
   }
-  const uint64_t fb = __ballot(live && (h.tops & kHalfFallback) != 0);
+  const uint64_t fb = __ballot(live && hit && (h.tops & kHalfFallback) != 0);
   if ((threadIdx.x & 63u) == 0 && t < cnt) fb_words[t >> 6] = fb;
+  if (A_CACHED) {  // the miss list: one atomic per wave
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool missed = live && !hit;
+    const uint64_t m = __ballot(missed);
+    if (m == 0) return;
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t b0 = 0;
+    if ((int)lane == leader) b0 = atomicAdd(miss_ctr, (uint32_t)__popcll(m));
+    b0 = __shfl(b0, leader);
+    if (missed) miss[b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;
+  }
 }
 
 
@@ -559,107 +631,48 @@ __global__ __launch_bounds__(kBlock, 4) void key_decode_kernel(const uint8_t* __
 }
 
 // ---- decoded-key cache (stl_keycache.h) ----
-// Ahead of verify_prep_kernel<.., true>, for chunks that run one lane per
+// After verify_prep_kernel<.., true>, for chunks that run one lane per
 // signature without key dedup:
-//   key_cache_lookup_kernel  one lane per row: gathers the tags of the key's
-//                            set, and a way with the key's tag offers its x; a
-//                            certified x goes into the row's state, any other
-//                            row onto the chunk's miss list;
-//   key_cache_fill_kernel    one lane per missed row, compacted: the full
-//                            decoding, its x and verdict into the row's state,
-//                            and a decodable key with x != 0 into the cache.
-// Both write words 20-31 of the row's HalfState: x(-A) as 9 canonical limbs
-// (the same limbs on a hit and on a miss), word 29 = the decoding is ok.
-__device__ __forceinline__ void st_key_ready(uint4* __restrict__ pre, uint32_t t, const fe& X, bool ok) {
-  uint4* q = pre + (size_t)t * 14 + kKeyReadyQuad;
-  st_state(q, make_uint4(X.v[0], X.v[1], X.v[2], X.v[3]));
-  st_state(q + 1, make_uint4(X.v[4], X.v[5], X.v[6], X.v[7]));
-  st_state(q + 2, make_uint4(X.v[8], ok ? 1u : 0u, 0u, 0u));
-}
+//   key_cache_fill_kernel    fill and finish, one lane per missed row,
+//                            compacted: the full decoding of A, a decodable
+//                            key with x != 0 into the cache, then the row's
+//                            state finished (finish_phase1_points) from the -Q
+//                            and flag prep left there -- P1, P2 and `tops` as
+//                            a hit lane of prep writes them (x(-A) as the same
+//                            canonical limbs on a hit and on a miss), and the
+//                            row's fallback bit ORed into its wave's word.
 
-// The set's tags (words 0-11 of the set: three quads) against the key's tag:
-// bit w = way w holds it.
-__device__ __forceinline__ uint32_t tag_matches(const uint4 t[3], const uint32_t tag[2]) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    m |= (t[i].x == tag[0] && t[i].y == tag[1]) ? 1u << (2 * i) : 0u;
-    m |= (t[i].z == tag[0] && t[i].w == tag[1]) ? 2u << (2 * i) : 0u;
-  }
-  return m;
-}
-static_assert(kKeyCacheWays == 6 && kKeyCacheTagWord == 0 && kKeyCacheXWord == 16, "tag_matches and the kernels below");
-
-__global__ __launch_bounds__(kBlock) void key_cache_lookup_kernel(const uint8_t* __restrict__ pk, uint32_t base,
-                                                                  uint32_t cnt, const uint4* cache, uint32_t mask,
-                                                                  uint4* __restrict__ pre, uint32_t* __restrict__ miss,
-                                                                  uint32_t* __restrict__ miss_ctr) {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63u;
-  const bool live = t < cnt;
-  uint32_t A[8];
-  ld8(A, pk + 32 * ((size_t)base + (live ? t : cnt - 1)));
-  const uint4* set = cache + (size_t)key_cache_set(key_hash(A), mask) * (kKeyCacheSetBytes / 16);
-  uint32_t tag[2];
-  key_cache_tag(tag, A);
+// What an insert sees of one set: bit w of `same` = way w holds the key's
+// tag, of `empty` = way w is all zero.
+__device__ __forceinline__ void key_cache_set_state(uint32_t& same, uint32_t& empty, const uint4* set,
+                                                    const uint32_t tag[2]) {
   const uint4 tq[3] = {set[0], set[1], set[2]};
-  const uint32_t match = tag_matches(tq, tag);
-  const int way = match ? __ffs((int)match) - 1 : -1;  // the lowest way with the key's tag
-  bool hit = false;
-  fe X;
-  if (__ballot(way >= 0) != 0) {  // a cold wave skips the check
-    uint32_t xb[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (way >= 0) {
-      const uint4 a = set[kKeyCacheXWord / 4 + 2 * way], b = set[kKeyCacheXWord / 4 + 2 * way + 1];
-      xb[0] = a.x; xb[1] = a.y; xb[2] = a.z; xb[3] = a.w;
-      xb[4] = b.x; xb[5] = b.y; xb[6] = b.z; xb[7] = b.w;
-    }
-    hit = key_cache_certify(X, A, xb) && way >= 0 && live;
+  same = tag_matches(tq, tag);
+  const uint32_t tw[12] = {tq[0].x, tq[0].y, tq[0].z, tq[0].w, tq[1].x, tq[1].y,
+                           tq[1].z, tq[1].w, tq[2].x, tq[2].y, tq[2].z, tq[2].w};
+  empty = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyCacheWays; ++w) {
+    const uint4 c = set[kKeyCacheXWord / 4 + 2 * w], d = set[kKeyCacheXWord / 4 + 2 * w + 1];
+    if ((tw[2 * w] | tw[2 * w + 1] | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w) == 0u) empty |= 1u << w;
   }
-  if (hit) st_key_ready(pre, t, X, true);
-  // the miss list: one atomic per wave
-  const bool missed = live && !hit;
-  const uint64_t m = __ballot(missed);
-  if (m == 0) return;
-  const int leader = __ffsll((unsigned long long)m) - 1;
-  uint32_t b0 = 0;
-  if ((int)lane == leader) b0 = atomicAdd(miss_ctr, (uint32_t)__popcll(m));
-  b0 = __shfl(b0, leader);
-  if (missed) miss[b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;
 }
 
-// One missed row t of the chunk: decoded, into its state and (if cacheable) the cache.
-__device__ __forceinline__ void key_cache_fill_row(const uint8_t* __restrict__ pk, uint32_t base, uint4* cache,
-                                                   uint32_t mask, uint4* __restrict__ pre, uint32_t t) {
-  uint32_t A[8];
-  ld8(A, pk + 32 * ((size_t)base + t));
-  ge_p3 negA;
-  const bool ok = ge_frombytes_negate_vartime(negA, A);
-  uint32_t xb[8];
-  fe_tobytes(xb, negA.X);
-  fe X;
-  fe_frombytes(X, xb);
-  st_key_ready(pre, t, X, ok);
-  uint32_t nz = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) nz |= xb[k];
-  if (!ok || nz == 0) return;  // never cached: such a key takes the chain every time
+// Key A with x(-A) = xb into the cache (key_cache_place: its primary set, or
+// the alternate one where the primary offers neither its tag nor an empty way).
+__device__ __forceinline__ void key_cache_insert(uint4* cache, uint32_t mask, const uint32_t A[8],
+                                                 const uint32_t xb[8]) {
   const uint32_t h = key_hash(A);
   uint4* set = cache + (size_t)key_cache_set(h, mask) * (kKeyCacheSetBytes / 16);
   uint32_t tag[2];
   key_cache_tag(tag, A);
-  const uint4 tq[3] = {set[0], set[1], set[2]};
-  const uint32_t match = tag_matches(tq, tag);
-  const uint32_t tw[12] = {tq[0].x, tq[0].y, tq[0].z, tq[0].w, tq[1].x, tq[1].y,
-                           tq[1].z, tq[1].w, tq[2].x, tq[2].y, tq[2].z, tq[2].w};
-  bool same[kKeyCacheWays], empty[kKeyCacheWays];
-#pragma unroll
-  for (uint32_t w = 0; w < kKeyCacheWays; ++w) {
-    const uint4 c = set[kKeyCacheXWord / 4 + 2 * w], d = set[kKeyCacheXWord / 4 + 2 * w + 1];
-    same[w] = ((match >> w) & 1u) != 0;
-    empty[w] = (tw[2 * w] | tw[2 * w + 1] | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w) == 0u;
-  }
-  const uint32_t v = key_cache_victim(h, same, empty);
+  uint32_t same0, empty0, same1 = 0, empty1 = 0;
+  key_cache_set_state(same0, empty0, set, tag);
+  uint4* aset = cache + (size_t)key_cache_alt_set(A, mask) * (kKeyCacheSetBytes / 16);
+  if ((same0 | empty0) == 0u) key_cache_set_state(same1, empty1, aset, tag);
+  bool alt;
+  const uint32_t v = key_cache_place(h, same0, empty0, same1, empty1, alt);
+  if (alt) set = aset;
   // plain stores: a reader that sees part of them fails its check and misses
   uint32_t* sw = reinterpret_cast<uint32_t*>(set);
   *reinterpret_cast<uint2*>(sw + kKeyCacheTagWord + 2 * v) = make_uint2(tag[0], tag[1]);
@@ -668,16 +681,50 @@ __device__ __forceinline__ void key_cache_fill_row(const uint8_t* __restrict__ p
   xs[1] = make_uint4(xb[4], xb[5], xb[6], xb[7]);
 }
 
+// One missed row t of the chunk: A decoded, (if cacheable) into the cache, and the row's state finished.
+__device__ __forceinline__ void key_cache_fill_row(const uint8_t* __restrict__ pk, uint32_t base, uint32_t policy,
+                                                   uint4* cache, uint32_t mask, uint4* __restrict__ pre,
+                                                   uint64_t* fb_words, uint32_t t) {
+  uint32_t A[8];
+  ld8(A, pk + 32 * ((size_t)base + t));
+  ge_p3 negA;
+  const bool ok = ge_frombytes_negate_vartime(negA, A);
+  uint32_t xb[8];
+  fe_tobytes(xb, negA.X);
+  uint32_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) nz |= xb[k];
+  // a key that does not decode, or with x == 0, is never cached: it takes the chain every time
+  if (ok && nz != 0) key_cache_insert(cache, mask, A, xb);
+  uint4* q = pre + (size_t)t * 14;
+  HalfState h;
+  ld_state_words<14>(h, q);
+  fe X;
+  fe_frombytes(X, xb);
+  const fe nAy = negA.Y, nQx = h.P2x, nQy = h.P2y;
+  finish_phase1_points(h, X, nAy, nQx, nQy, ok && (h.pad & kMissPointOk) != 0);
+  if ((policy & kModeFullLength) && (h.tops & kHalfOk)) h.tops |= kHalfFallback;
+  h.pad = 0;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(&h);
+  st_state(q + kHalfTopsWord / 4, make_uint4(w[8], w[9], w[10], w[11]));
+#pragma unroll
+  for (int i = kHalfScalarQuads - 1; i < 14; ++i)  // from quad 4: pad is its last word
+    st_state(q + i, make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]));
+  static_assert(offsetof(HalfState, pad) == 4 * (4 * kHalfScalarQuads - 1), "pad ends the scalar quads");
+  // prep's ballot did not know this row's flag
+  if (h.tops & kHalfFallback) atomicOr(reinterpret_cast<unsigned long long*>(&fb_words[t >> 6]), 1ull << (t & 63u));
+}
+
 // The grid covers cnt rows (the host cannot know the miss count); lanes past
 // the count exit.  A grid capped at the resident workgroups, striding over the
 // list, measured slower cold (0.89 vs 0.82 ms per 2^20 misses) and the same
-// warm: the 0.09 ms a warm 2^20-row chunk spends here is one wave's latency
-// through the chain for its last hundred misses, not the empty workgroups.
+// warm.  A launch whose rows all hit costs an empty launch here.
 // Lane 0 adds the chunk's hits and misses to the device's statistics
 // (counters[2], [3]).
 __global__ __launch_bounds__(kBlock, 4) void key_cache_fill_kernel(const uint8_t* __restrict__ pk, uint32_t base,
-                                                                   uint32_t cnt, uint4* cache, uint32_t mask,
-                                                                   uint4* __restrict__ pre,
+                                                                   uint32_t cnt, uint32_t policy, uint4* cache,
+                                                                   uint32_t mask, uint4* __restrict__ pre,
+                                                                   uint64_t* fb_words,
                                                                    const uint32_t* __restrict__ miss,
                                                                    const uint32_t* __restrict__ miss_ctr,
                                                                    unsigned long long* __restrict__ counters) {
@@ -688,7 +735,7 @@ __global__ __launch_bounds__(kBlock, 4) void key_cache_fill_kernel(const uint8_t
     atomicAdd(&counters[3], (unsigned long long)nm);
   }
   if (i >= nm) return;  // no wave-level collective in this kernel
-  key_cache_fill_row(pk, base, cache, mask, pre, miss[i]);
+  key_cache_fill_row(pk, base, policy, cache, mask, pre, fb_words, miss[i]);
 }
 
 // The chunk's wide key tables j*(-A), j = 0..136, in two stages
@@ -2097,24 +2144,23 @@ static hipError_t verify_chunk(const uint8_t* sig, const uint8_t* msg_or_k, cons
         hipLaunchKernelGGL(verify_prep_pair_kernel<false>, dim3(nblk), dim3(kBlock), 0, stream, sig, msg_or_k,
                            pk, base, cnt, policy, pre, nbs);
     } else if (fused && x.key_cache && mctr) {
-      // the keys' x from the device's cache where it certifies, decoded (and
-      // cached) where not; then phase 1 with only R's square root
-      hipLaunchKernelGGL(key_cache_lookup_kernel, g1, dim3(kBlock), 0, stream, pk, base, cnt, x.key_cache,
-                         x.key_cache_mask, pre, miss, mctr);
-      hipLaunchKernelGGL(key_cache_fill_kernel, g1, dim3(kBlock), 0, stream, pk, base, cnt, x.key_cache,
-                         x.key_cache_mask, pre, miss, mctr, counters);
+      // phase 1 with only R's square root and the keys' x from the device's
+      // cache where it certifies; then the missed rows' keys decoded (and
+      // cached) and their states finished
       if (pre_k)
         hipLaunchKernelGGL((verify_prep_kernel<true, true>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
-                           policy, pre, fb);
+                           policy, pre, fb, x.key_cache, x.key_cache_mask, miss, mctr);
       else
         hipLaunchKernelGGL((verify_prep_kernel<false, true>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
-                           policy, pre, fb);
+                           policy, pre, fb, x.key_cache, x.key_cache_mask, miss, mctr);
+      hipLaunchKernelGGL(key_cache_fill_kernel, g1, dim3(kBlock), 0, stream, pk, base, cnt, policy, x.key_cache,
+                         x.key_cache_mask, pre, fb, miss, mctr, counters);
     } else if (fused && pre_k)
       hipLaunchKernelGGL((verify_prep_kernel<true, false>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
-                         policy, pre, fb);
+                         policy, pre, fb, nullptr, 0u, nullptr, nullptr);
     else if (fused)
       hipLaunchKernelGGL((verify_prep_kernel<false, false>), g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt,
-                         policy, pre, fb);
+                         policy, pre, fb, nullptr, 0u, nullptr, nullptr);
     else if (pre_k)
       hipLaunchKernelGGL(verify_scalar_kernel<true>, g1, dim3(kBlock), 0, stream, sig, msg_or_k, pk, base, cnt, pre);
     else

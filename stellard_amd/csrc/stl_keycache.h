@@ -47,6 +47,14 @@
 // The set index is key_hash & (2^K - 1); the way an insert starts from comes
 // from the hash's top byte, which no mask up to 2^24 uses.
 //
+// Those 0.06 % (about 600 of 2^20 keys) would miss on every call.  So a key has
+// a second-choice set (key_cache_alt_set, from the key alone, never its
+// primary set): an insert goes there only when the primary set holds neither
+// the key's tag nor an empty way (key_cache_place), and a lookup reads the
+// alternate set's tags only when the primary set's hold no match -- a warm
+// lookup still gathers one set for all but those keys.  What either set offers
+// goes through the same check.
+//
 // Plain C++ for the host and the device (tests/native/hostemu_keycache.cpp).
 #pragma once
 #include "stl_fe25519.h"
@@ -78,6 +86,27 @@ STL_HD uint32_t key_hash(const uint32_t A[8]) {
 STL_HD uint32_t key_cache_set(uint32_t hash, uint32_t mask) { return hash & mask; }
 STL_HD uint32_t key_cache_first_way(uint32_t hash) { return ((hash >> 24) * kKeyCacheWays) >> 8; }
 static_assert(kKeyCacheLog2Max <= 24, "the way bits lie above every set mask");
+// The key's second-choice set.  key_hash's 32 bits are all spoken for at the
+// largest mask (24 of set index, 8 of first way), so the offset from the
+// primary set comes from a second word of hash over the key, mixed from the
+// four words key_hash leaves out or weighs least: a function of the key alone
+// and independent of the primary index.  The offset is forced non-zero inside
+// the mask (its lowest bit, where the hash's bits there are all zero), so the
+// two sets differ whenever the mask has a bit, i.e. more than one set is in
+// use; with mask 0 both are set 0.
+STL_HD uint32_t key_cache_alt_set(const uint32_t A[8], uint32_t mask) {
+  uint32_t g = A[3] * 0xC2B2AE35u;
+  g ^= A[6] * 0x27D4EB2Fu;
+  g = (g << 15) | (g >> 17);
+  g ^= A[4] * 0x9E3779B1u;
+  g ^= A[7] * 0x85EBCA6Bu;
+  g ^= g >> 15;
+  g *= 0x2C1B3C6Du;
+  g ^= g >> 13;
+  uint32_t off = g & mask;
+  if (off == 0) off = mask & (0u - mask);
+  return key_cache_set(key_hash(A), mask) ^ off;
+}
 // The key's tag, from the words key_hash leaves out and the two it weighs
 // least: independent of the set index.
 STL_HD void key_cache_tag(uint32_t tag[2], const uint32_t A[8]) {
@@ -104,6 +133,30 @@ STL_HD uint32_t key_cache_victim(uint32_t hash, const bool same[kKeyCacheWays], 
   for (int w = (int)kKeyCacheWays - 1; w >= 0; --w)  // the lowest such way: the one a lookup tries
     if (same[w]) v = (uint32_t)w;
   return v;
+}
+
+// Where an insert writes, over the key's two sets (bit w of same0 / empty0:
+// way w of the primary set holds the key's tag / is all zero; same1 / empty1
+// likewise for the alternate set, which a caller need only read when the
+// primary set offers nothing and may pass as 0, 0 otherwise).  An insert
+// writes where the next lookup looks first:
+//   1. the way holding the key's tag in the primary set,
+//   2. an empty primary way (key_cache_victim),
+//   3. the way holding the key's tag in the alternate set,
+//   4. an empty alternate way (key_cache_victim in that set),
+//   5. the primary set's hash way.
+// Returns the way; `alt` says which set.
+STL_HD uint32_t key_cache_place(uint32_t hash, uint32_t same0, uint32_t empty0, uint32_t same1, uint32_t empty1,
+                                bool& alt) {
+  alt = (same0 | empty0) == 0u && (same1 | empty1) != 0u;
+  const uint32_t sb = alt ? same1 : same0, eb = alt ? empty1 : empty0;
+  bool same[kKeyCacheWays], empty[kKeyCacheWays];
+#pragma unroll
+  for (uint32_t w = 0; w < kKeyCacheWays; ++w) {
+    same[w] = ((sb >> w) & 1u) != 0;
+    empty[w] = ((eb >> w) & 1u) != 0;
+  }
+  return key_cache_victim(hash, same, empty);
 }
 
 // Branch-free.  X = fe_frombytes(xbytes); true iff X is the x of -A as

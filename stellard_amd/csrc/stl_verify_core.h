@@ -467,18 +467,33 @@ STL_HD bool phase1_points_ok(const uint32_t R[8], const uint32_t S[8], const uin
   return verify_prechecks(R, S, A, policy) && composite_s_ok(S, policy) && r_is_canonical(R) && okA && okR;
 }
 
-// Phase 1, point half, with -A decoded once per distinct key of the batch
+// Phase 1, point half, in two steps for rows whose -A comes from elsewhere
+// (the per-batch key table, the decoded-key cache, or its fill kernel after a
+// miss).  First everything that needs no decoded A: the pre-checks (on the
+// key's bytes), stellard's S < L, a canonical R and R's decoding -Q; returns
+// whether all of them passed.  Then finish_phase1_points with -A, -Q and
+// (this flag && A's decoding is ok) -- in the same lane, or later from the
+// -Q and flag kept in the row's state.
+STL_HD bool verify_phase1_points_r(fe& nQx, fe& nQy, const uint32_t R[8], const uint32_t S[8], const uint32_t A[8],
+                                   uint32_t policy) {
+  bool ok = verify_prechecks(R, S, A, policy);
+  ok = ok && composite_s_ok(S, policy) && r_is_canonical(R);
+  ge_p3 negQ;
+  const bool okR = ge_frombytes_negate_vartime(negQ, R);
+  nQx = negQ.X;
+  nQy = negQ.Y;
+  return ok && okR;
+}
+
+// Both steps in one lane, with -A decoded once per distinct key of the batch
 // (STL_DEDUP_KEYS: many transactions share a signer): decodes only R.  The
 // key's decoding is a function of its 32 bytes alone, so the result is the
 // same as decoding it in every lane.
 STL_HD void verify_phase1_points_keyed(HalfState& o, const uint32_t R[8], const uint32_t S[8], const uint32_t A[8],
                                        uint32_t policy, const fe& negAx, const fe& negAy, bool okA) {
-  bool ok = verify_prechecks(R, S, A, policy);
-  ok = ok && composite_s_ok(S, policy) && r_is_canonical(R);
-  ge_p3 negQ;
-  const bool okR = ge_frombytes_negate_vartime(negQ, R);
-  ok = ok && okA && okR;
-  finish_phase1_points(o, negAx, negAy, negQ.X, negQ.Y, ok);
+  fe nQx, nQy;
+  const bool okr = verify_phase1_points_r(nQx, nQy, R, S, A, policy);
+  finish_phase1_points(o, negAx, negAy, nQx, nQy, okr && okA);
 }
 
 STL_HD void verify_phase1_half(HalfState& o, const uint32_t R[8], const uint32_t S[8], const uint32_t A[8],
